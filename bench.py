@@ -3,23 +3,33 @@
 (BASELINE.json: N = dv = 50 horizon stages, k_max = 10, fp64), closed loop with the example's forward-Euler
 plant, everything resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
 
 One "step" = one control tick of the whole batch; the closed loop runs on the device and the tick kernel advances
 cgmres_cpp_amd.TICKS_PER_LAUNCH (10) consecutive ticks per launch.
 
+A plain run sets up, warms up, times exactly K steps once (`ms_per_step` = wall time of the K steps / K), writes the
+outputs of the last step if --dump-outputs is given and prints the line.  Everything else is behind --full: the
+oracle parity gate, the timed region repeated --reps (5) times with the MEDIAN repetition reported, the reference-mode
+(tol = 1e-6) and early-exit placement legs, the CPU baseline and, for N > 1, the weak-scaling figure.
+
+--dump-outputs DIR: after the timed steps, what a caller of the closed loop holds after its last step — the plant
+state x [batch, 4] and controls u [batch, 3] — and the controller state it can read back (U and dUdt of get_state, as
+U_horizon and dUdt_horizon [batch, 150]), gathered over the ranks in global instance order, as DIR/<name>.npy
+(float64).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
 Scaling: the metric is a FIXED batch of 4096 controllers at 1/2/4/8 GPUs, so `value` is STRONG scaling — the 4096
 instances are split into contiguous shards (cgmres_cpp_amd.sharding.shard_bounds), one process per GPU; rank 0
 draws the seeded job and the shards go out once over RCCL; there is no collective inside the timed region
-(instances are independent).  For N > 1 the weak-scaling figure (4096 controllers per GPU) is measured in the same
-run and reported under "weak_scaling".
+(instances are independent).  For N > 1, --full also measures the weak-scaling figure (4096 controllers per GPU) and
+reports it under "weak_scaling".
 
 The timed region (exactly K steps, barrier + synchronize on both sides, max over ranks) is repeated --reps times
 back to back on the continuing closed loop; `value`/`ms_per_step` are the MEDIAN repetition.
 
-Parity gate: before the line is printed, a spread sample of the instances this process just timed is checked against
-the oracle (oracle/liboracle.so, the checker — never the thing measured): free-running over the warm-up ticks
+Parity gate (--full): before the line is printed, a spread sample of the instances this process just timed is checked
+against the oracle (oracle/liboracle.so, the checker — never the thing measured): free-running over the warm-up ticks
 (<= 100 ticks: 1e-9 on u and x), and — from the controller/plant state left by the timed
 region — one teacher-forced tick at 1e-9 followed by a full fused launch of 10 free-running ticks at 1e-6 (the
 closed loop amplifies rounding differences; see the comment at the check).
@@ -42,6 +52,7 @@ FP64_VALU_PEAK_TFLOPS = 78.6  # MI355X_MICROARCH.md: vector fp64 (256 CU x 4 SIM
 MODEL, MODEL_ID, DV, KMAX = "pendulum", 0, 50, 10
 DIM_X, DIM_U, DIM_P = 4, 3, 2
 GLOBAL_BATCH = 4096
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most 64 MiB in all
 # rocprofv3 PMC summary of this same command (tools/profile_bench.sh + tools/summarise_profile.py), newest first
 ISSUE_MODELS = [os.path.join(ROOT, "profiles", n) for n in ("r03_issue_model.json", "r02_issue_model.json")]
 INSTRUCTION_COUNTERS = os.path.join(ROOT, "profiles", "r04_wg_instruction_counters.json")
@@ -186,7 +197,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed K-step region (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity gate, the secondary legs (reference mode, early-exit placement, CPU "
+                         "baseline, weak scaling for N > 1) and repeat the timed region --reps times")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write x, u, U_horizon, dUdt_horizon of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the timed K-step region (median reported); default 1, or 5 with --full")
     ap.add_argument("--batch", type=int, default=GLOBAL_BATCH, help="GLOBAL batch (split over the GPUs)")
     ap.add_argument("--tol", type=float, default=0.0,
                     help="0 = fixed-k mode (always k_max Arnoldi iterations, deterministic work; headline); "
@@ -204,7 +221,8 @@ def main():
                     help="global batch of the early-exit placement measurement (needs more workgroups than the GPU "
                          "holds at once; 0 = skip)")
     ap.add_argument("--no-weak", action="store_true", help="N > 1: skip the secondary weak-scaling measurement")
-    ap.add_argument("--check-sample", type=int, default=48, help="instances per rank checked against the oracle")
+    ap.add_argument("--check-sample", type=int, default=48,
+                    help="instances per rank checked against the oracle (--full)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the real thing); gloo = rehearsal of the N > 1 path on a box with fewer "
                          "GPUs than ranks (ranks share devices, collectives go through host tensors)")
@@ -212,6 +230,10 @@ def main():
                     help="rendezvous only: every rank joins the process group, rank 0 prints the world it sees (the "
                          "CPU rehearsal of the N > 1 entry; needs no GPU)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    if args.steps < 1 or args.reps < 1:
+        ap.error("--steps and --reps must be >= 1")
 
     # N > 1 started like N = 1 (no torch.distributed.run around it): become the launcher.  Decided BEFORE torch is
     # imported, so the parent never initialises the GPU.
@@ -283,13 +305,39 @@ def main():
         us, _, _, _ = orc.closed_loop(c, x0, ticks)
         return bool((~np.isfinite(us)).any() or np.nanmax(np.abs(us)) > 1e6)
 
-    def measure(inputs, tol, steps, warmup, reps, check, flags=None, fatal=True, also_fixed_k=False):
+    def dump_outputs(out_dir, ctrl, x, u):
+        """What the timed closed loop left after its last step, gathered in global instance order (the shards are
+        contiguous by rank) and written by rank 0 as float64 .npy files.  Beyond DUMP_LIMIT_BYTES a fixed, seeded sample
+        of instances is written, with their global indices in instances.npy."""
+        _, U, d = ctrl.get_state()
+        mine = {"x": x.cpu().numpy(), "u": u.cpu().numpy(), "U_horizon": U, "dUdt_horizon": d}
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, mine)
+        else:
+            parts = [mine]
+        if rank != 0:
+            return
+        full = {k: np.concatenate([p[k] for p in parts]).astype(np.float64) for k in mine}
+        n = len(full["x"])
+        per_instance = sum(a[0].nbytes for a in full.values())
+        if n * per_instance > DUMP_LIMIT_BYTES:
+            n_keep = (DUMP_LIMIT_BYTES - 4096) // (per_instance + 8)  # (+ the index column; 4 KiB for the headers)
+            keep = np.sort(np.random.default_rng(2024).choice(n, n_keep, replace=False))
+            full = {k: a[keep] for k, a in full.items()}
+            full["instances"] = keep.astype(np.float64)
+        os.makedirs(out_dir, exist_ok=True)
+        for k, a in full.items():
+            np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+
+    def measure(inputs, tol, steps, warmup, reps, check, flags=None, fatal=True, also_fixed_k=False, dump=None):
         """Closed loop of this rank's shard: warm-up, then `reps` timed regions of exactly `steps` ticks.
         A failed parity gate ends the script (the headline: no number without parity) or, for a SECONDARY leg
         (fatal=False), comes back as {"error": ...} so that the leg is reported as failed without a number.
         also_fixed_k: a second controller batch with tol = 0 takes over the state the warm-up left (t, U, dUdt, x) and
         is timed for `steps` ticks from there — the fixed-k figure for the SAME controller/plant state as the early-exit
-        leg that follows (its result is not fed back)."""
+        leg that follows (its result is not fed back).
+        dump: directory for the outputs of the last timed step (dump_outputs)."""
         x0_h, u0_h, p_h = inputs
         B = len(x0_h)
         ctrl = cg.CgmresBatch(MODEL, batch=B, dv=DV, k_max=KMAX, tol=tol, device=local, stream=stream,
@@ -352,6 +400,8 @@ def main():
             if world > 1:
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             walls.append(tt[0].item()), kernels.append(tt[1].item())
+        if dump:
+            dump_outputs(dump, ctrl, x, u)
         n_ax, why = ctrl.get_status()
         # Non-finite instances.  C/GMRES itself can diverge: on this seeded scenario the REFERENCE's own closed loop of
         # instance 3599 runs to |u| ~ 1e12 and NaN at tick 4695 in early-exit mode (the slack input crosses zero; with
@@ -403,8 +453,10 @@ def main():
                 "fixed_k_same_state": fixed_k_ms}
 
     n_check = args.check_sample if world == 1 else max(8, args.check_sample // world)
+    if not args.full:
+        n_check = 0  # (the oracle gate is part of --full)
     inputs = shard_inputs(args.batch)
-    m = measure(inputs, args.tol, args.steps, args.warmup, args.reps, n_check)
+    m = measure(inputs, args.tol, args.steps, args.warmup, args.reps, n_check, dump=args.dump_outputs)
     head = dict(resolved)  # (the mapping of the HEADLINE leg: the secondary legs below resolve their own)
     B = m["B"]
     value = args.batch * args.steps / m["wall"]
@@ -451,7 +503,7 @@ def main():
             return {"error": f"{type(e).__name__}: {e}"}
 
     ref_mode = binning = None
-    if not args.no_ref_mode and args.tol == 0.0:
+    if args.full and not args.no_ref_mode and args.tol == 0.0:
         reps2 = max(1, min(args.reps, 3))
         ref_mode = early_exit_leg(soft(lambda: measure(inputs, 1e-6, args.steps, args.ref_warmup, reps2, n_check,
                                                        fatal=False, also_fixed_k=True)), args.batch, args.ref_warmup)
@@ -475,7 +527,7 @@ def main():
             both = legs["binned_by_last_count"]["value"] and legs["caller_order"]["value"]
             binning = dict(legs, speedup=(legs["binned_by_last_count"]["value"] / legs["caller_order"]["value"]) if both else None)
     weak = None
-    if world > 1 and not args.no_weak:
+    if args.full and world > 1 and not args.no_weak:
         mw = measure(shard_inputs(args.batch * world), args.tol, args.steps, args.warmup, max(1, min(args.reps, 3)), 0,
                      fatal=False)
         weak = {"scaling": "weak", "global_batch": args.batch * world, "value": None, "parity_failure": mw["error"]} \
@@ -545,7 +597,7 @@ def main():
         out["early_exit_placement"] = binning
     if weak:
         out["weak_scaling"] = weak
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.batch, args.tol, min(args.warmup, 50) or 5, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -119,3 +119,13 @@ def test_bench_handles_every_fused_variant_in_its_bookkeeping(monkeypatch):
     assert b.KERNEL_OF_VARIANT[4] == "tick_wave_kernel"
     # the secondary (VALU) view: SURVEY.md 8(d)'s flop count of one pendulum instance-tick at k = 10
     assert b.algorithmic_flops(10) == 13 * 50 * 111 + 13 * 600 + 4 * 150 * 55 + 4500 + 14 * 300
+
+
+def test_bench_has_the_full_and_dump_options():
+    """A plain run measures the headline only; the secondary legs are behind --full, the arrays of the last timed step
+    behind --dump-outputs DIR (tests/test_gpu_bench_plain.py runs both on the device)."""
+    r = _run_plain("bench.py", "--help")
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+    b = _bench()
+    assert b.DUMP_LIMIT_BYTES == 64 << 20

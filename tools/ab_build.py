@@ -40,7 +40,7 @@ else:
             extra = ["--flags", str(int(sw[2:], 0))] if sw.startswith("f=") else {"serial": ["--flags", "1"], "twopass": ["--flags", "8"], "": []}[sw]  # CGMRES_HIP_FLAG_*
             if lib != "base":
                 env["CGMRES_HIP_LIB"] = os.path.join(AB, lib, "lib.so")
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-ref-mode", "--steps", "150", "--warmup", "30"] + extra + os.environ.get("AB_BENCH_ARGS", "").split(),
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-ref-mode", "--steps", "150", "--warmup", "30"] + extra + os.environ.get("AB_BENCH_ARGS", "").split(),
                                env=env, capture_output=True, text=True)
             res[n].append(json.loads(r.stdout.strip().split("\n")[-1])["ms_per_step"])
     for n in names:
