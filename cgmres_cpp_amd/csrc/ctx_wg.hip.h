@@ -66,8 +66,15 @@ struct CtxWg final : cgmres_hip_ctx {
   struct RowAffine<MM, std::void_t<decltype(MM::ROW_AFFINE)>> : std::integral_constant<bool, MM::ROW_AFFINE> {};
   static constexpr int kWaveKmax = 10, kWaveWpb = 1;
   size_t lds_bytes_tick() const { return wave ? WaveLds<M, T>::bytes(cfg.dv, cfg.k_max, kWaveWpb) : lds_bytes; }
+  // user models (WaveOps<UserDev<Model>>): fp64, dim_x <= kUserWaveMaxNx, dim_u <= kUserWaveMaxNu, and only on request
+  template <class MM, class = void>
+  struct WaveFits : std::true_type {};
+  template <class MM>
+  struct WaveFits<MM, std::void_t<decltype(WaveOps<MM>::FITS)>> : std::integral_constant<bool, WaveOps<MM>::FITS> {};
+  static constexpr bool kWave = WaveOps<M>::value && std::is_same<T, double>::value && WaveFits<M>::value;
+  static constexpr bool kWaveDefault = kWave && !WaveSerialState<M>::value;  // (the library's choice never takes user models)
   static bool wave_supported(const cgmres_hip_config& c) {
-    if constexpr (WaveOps<M>::value && std::is_same<T, double>::value)
+    if constexpr (kWave)
       return c.dv >= 1 && c.dv <= 63 && c.k_max >= 1 && c.k_max <= kWaveKmax;
     return false;
   }
@@ -186,9 +193,16 @@ struct CtxWg final : cgmres_hip_ctx {
     // tick in ~43 us (wg: ~117 us whatever the batch); the kernel takes all 512 registers, so a batch beyond one
     // controller per SIMD runs in rounds: two rounds (~88 us) still beat the wg mapping, three do not.
     if (cfg.variant == 4) {
+      if constexpr (WaveSerialState<M>::value) {
+        if (!wave_supported(cfg))
+          return fail(CGMRES_HIP_EINVAL,
+                      "wave mapping for a user model: needs dim_x <= %d (has %d), dim_u <= %d (has %d), 1 <= dv <= 63 "
+                      "(has %d), 1 <= k_max <= %d (has %d)",
+                      kUserWaveMaxNx, M::NX, kUserWaveMaxNu, M::NU, cfg.dv, kWaveKmax, cfg.k_max);
+      }
       if (!wave_supported(cfg)) return fail(CGMRES_HIP_EINVAL, "wave mapping: model / dtype / dv = %d / k_max = %d not supported", cfg.dv, cfg.k_max);
       wave = true;
-    } else if (cfg.variant == 0 && wave_supported(cfg) && cfg.batch <= 8 * cus && !(cfg.flags & CGMRES_HIP_FLAG_NO_WAVE)) {
+    } else if (cfg.variant == 0 && kWaveDefault && wave_supported(cfg) && cfg.batch <= 8 * cus && !(cfg.flags & CGMRES_HIP_FLAG_NO_WAVE)) {
       wave = true;
     }
     if (lean) plan = PLAN_LEAN, fh_hbm = 0, lds_bytes = lean_bytes;
@@ -217,7 +231,7 @@ struct CtxWg final : cgmres_hip_ctx {
     if (want == 16 && big) pick<16, 20>(lean, par);
     if (want == 8 && !big) pick<8, 10>(false, 0);
     if (want == 8 && big) pick<8, 20>(false, 0);
-    if constexpr (WaveOps<M>::value && std::is_same<T, double>::value) {
+    if constexpr (kWave) {
       if (wave) k_tick = tick_wave_kernel<M, T, kWaveKmax, kWaveWpb>;
     }
     // row-parallel scans for a state equation that is affine in x (WgCtx::NWT = 2): the full plan's 16-instance kernel

@@ -48,8 +48,9 @@ struct WaveLane {
 // from a base trajectory, serial sweeps in front of the solve (the code in the kernel); otherwise the model supplies
 //   state_scan  (L, u, xinit, dtau, x)            x(s) of every lane's stage from the lane's controls: ONE scan, exact
 //   costate_scan(L, x, u, p, dtau, phi, dF)       costate recurrence + dH/du pieces from the lane's stage
+// or, with SERIAL_STATE (user models), state_sweeps<NS>(L, u, xinit, dtau, p, x): NS serial sweeps side by side
 template <class M>
-struct WaveOps : std::false_type {  // (no wave scans: user models and whatever is not specialised below)
+struct WaveOps : std::false_type {  // (no wave scans: whatever is not specialised below)
   static constexpr bool NONLINEAR = false;
   static constexpr int LDS_EXTRA = 0;
 };
@@ -199,6 +200,110 @@ struct WaveOps<MsdDev<T>> : std::true_type {
   }
 };
 
+// USER models (user_model.hip.h), fp64.  Nothing is known about the state equation, so the state recurrence
+// x(s+1) = x(s) + dxdt(x(s), U(s), p(s)) dtau (cgmres.hpp:131-140) is walked SERIALLY inside the wave: a wave-uniform
+// loop over the stages, stage s's controls and parameters fetched with readlane, the model's dxdt on wave-uniform values,
+// x(s+1) kept by lane s+1.  No LDS.  state_sweeps<NS> runs NS independent sweeps in one loop so that their dependency
+// chains overlap (the three sweeps in front of the solve).  The costate recurrence is affine in the costate with the
+// coefficients UserDev::stage_coeffs generates by probing the user's dHdx / dHdu (checked on the device,
+// user_affinity_kernel): lambda(s) = (I + dtau J(s)^T) lambda(s+1) + dtau q(s) — one scan of NX x NX affine maps on
+// the mirrored lanes (scan_affn), and dF(s) = B(s)^T lambda(s+1) on the lane of stage s.
+// Limits (CtxWg::wave_supported): NX <= kUserWaveMaxNx — the scan keeps a map and its DPP partner (2 NX^2 + 2 NX
+// doubles) next to the register-resident Krylov basis; NU <= kUserWaveMaxNu (the basis is (k_max + 1) NU doubles per lane).
+constexpr int kUserWaveMaxNx = 4, kUserWaveMaxNu = 6;
+template <class Model>
+struct UserDev;
+template <class Model>
+struct WaveOps<UserDev<Model>> : std::true_type {
+  using M = UserDev<Model>;
+  using T = double;
+  static constexpr bool NONLINEAR = false;
+  static constexpr bool SERIAL_STATE = true;  // state_sweeps instead of state_scan; p of stage 0 in x_dxh and the plant
+  static constexpr bool FITS = M::NX <= kUserWaveMaxNx && M::NU <= kUserWaveMaxNu;
+  struct TickConsts {};
+  static constexpr int LDS_EXTRA = 0;
+  static __device__ __forceinline__ void make_consts(TickConsts&, T, const WaveLane&, T*) {}
+  // x[q] of every lane's stage (lane 0: xinit[q]; lanes beyond dv keep xinit[q]) for the controls u[q] on the lanes
+  template <int NS>
+  static __device__ __forceinline__ void state_sweeps(const WaveLane& L, const T (&u)[NS][M::NU], const T (&xinit)[NS][M::NX],
+                                                      const T (&dtau)[NS], const T* p, T (&x)[NS][M::NX]) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
+    T y[NS][NX];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+#pragma unroll
+      for (int c = 0; c < NX; ++c) y[q][c] = xinit[q][c], x[q][c] = xinit[q][c];
+    }
+    for (int s = 0; s < L.dv; ++s) {  // (wave-uniform)
+      T ps[NP > 0 ? NP : 1];
+      ps[0] = T(0);
+#pragma unroll
+      for (int j = 0; j < NP; ++j) ps[j] = wave_bcast(p[j], s);
+      const bool mine = L.lane == s + 1;
+#pragma unroll
+      for (int q = 0; q < NS; ++q) {
+        T us[NU], f[NX];
+#pragma unroll
+        for (int j = 0; j < NU; ++j) us[j] = wave_bcast(u[q][j], s);
+        M::dxdt_p(f, y[q], us, ps);
+#pragma unroll
+        for (int c = 0; c < NX; ++c) {
+          y[q][c] = f[c] * dtau[q] + y[q][c];
+          x[q][c] = mine ? y[q][c] : x[q][c];
+        }
+      }
+    }
+  }
+  static __device__ __forceinline__ void costate_scan(const WaveLane& L, const T* x, const T* u, const T* p, T dtau,
+                                                      const TickConsts&, T* phi, T* dF) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
+    T bw[M::NBW];
+    M::stage_coeffs(bw, phi, x, u, p, nullptr, dtau);
+    // terminal costate from the terminal stage (lane dv), wave-uniform (cgmres.hpp:146)
+    T xT[NX], pT[NP > 0 ? NP : 1], lT[NX];
+    pT[0] = T(0);
+#pragma unroll
+    for (int c = 0; c < NX; ++c) xT[c] = wave_bcast(x[c], L.dv);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) pT[j] = wave_bcast(p[j], L.dv);
+    M::dPhidx(lT, xT, pT);
+    // the map of stage dv-1-m on lane m: l -> l + D l + c with D = dtau J^T, c = dtau q; lane 0 applies its map to the
+    // terminal costate (c += (I + D) lT)
+    T D[NX * NX], c[NX];
+#pragma unroll
+    for (int e = 0; e < NX * NX; ++e) D[e] = wave_gather(bw[e], L.msrc);
+#pragma unroll
+    for (int r = 0; r < NX; ++r) c[r] = wave_gather(bw[M::NBW_LIN + r], L.msrc);
+    const bool first = L.lane == 0;
+    T y[NX];
+#pragma unroll
+    for (int r = 0; r < NX; ++r) y[r] = first ? lT[r] : T(0);
+#pragma unroll
+    for (int r = 0; r < NX; ++r) {
+      T a = c[r] + y[r];
+#pragma unroll
+      for (int k = 0; k < NX; ++k) a = fma_t(D[NX * r + k], y[k], a);
+      c[r] = a;
+    }
+    scan_affn<NX>(D, c);
+    // the costate ENTERING the stage, back on the stage's own lane: dF = B^T lambda(s+1) (cgmres.hpp:155-161)
+    T l[NX];
+#pragma unroll
+    for (int r = 0; r < NX; ++r) l[r] = wave_gather(wave_shift_up(c[r], lT[r]), L.msrc);
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+      T a = T(0);
+#pragma unroll
+      for (int k = 0; k < NX; ++k) a = fma_t(bw[NX * NX + j * NX + k], l[k], a);
+      dF[j] = a;
+    }
+  }
+};
+template <class M, class = void>
+struct WaveSerialState : std::false_type {};
+template <class M>
+struct WaveSerialState<M, std::void_t<decltype(WaveOps<M>::SERIAL_STATE)>> : std::integral_constant<bool, WaveOps<M>::SERIAL_STATE> {};
+
 // LDS of one wave: the table of the serial sweeps and two control rows for them (nothing else lives in memory)
 template <class M, class T>
 struct WaveLds {
@@ -260,6 +365,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(VLDS ?
   using Lds = WaveLds<M, T>;
   constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NC = M::NC, NUL = M::NUL;
   constexpr bool NONLIN = W::NONLINEAR;
+  constexpr bool SERIAL = WaveSerialState<M>::value;  // user models: serial state sweeps, dxdt reads p
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
@@ -306,6 +412,16 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(VLDS ?
   }
   int n_ax = 0, reason = 0, ksolve = 0;
   T xh[NX];
+  // the state equation at the stage-0 parameters (user models read p in dxdt: cgmres.hpp:83, WgCtx::model_dxdt)
+  auto dxdt_p0 = [&](T* f, const T* x, const T* u) {
+    if constexpr (SERIAL) {
+      T p0[NP > 0 ? NP : 1];
+      p0[0] = T(0);
+#pragma unroll
+      for (int j = 0; j < NP; ++j) p0[j] = wave_bcast(p[j], 0);
+      M::dxdt_p(f, x, u, p0);
+    }
+  };
 
   // ---- phase 3 of a sweep on the lanes: costate recurrence + the costate part of dH/du (cgmres.hpp:145-161) from the
   //      stage's state / trig / controls.  Returns phi (costate-free part of dH/du) and dF (to be added to component 0).
@@ -466,13 +582,34 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(VLDS ?
       T u0[NU], f[NX], tr[NC > 0 ? NC : 1];
 #pragma unroll
       for (int j = 0; j < NU; ++j) u0[j] = wave_bcast(U[j], 0);
-      M::dxdt(f, xs, u0, tr, mc);
+      if constexpr (SERIAL)
+        dxdt_p0(f, xs, u0);
+      else
+        M::dxdt(f, xs, u0, tr, mc);
 #pragma unroll
       for (int c = 0; c < NX; ++c) xh[c] = f[c] * P.h + xs[c];
     }
     T xb[NX], tb[4];  // NONLINEAR: base trajectory of this tick (sweep #1) on the lanes
     T bb[NU], ax0[NU];
-    if constexpr (!NONLIN) {
+    if constexpr (SERIAL) {
+      // ---- the three sweeps in front of the solve: state sweeps #1 (U, x+hf, t+h), #2 (U, x, t), #3 (U+h dUdt, x+hf,
+      //      t+h) interleaved in one serial loop, then one costate scan each
+      T us[3][NU], x0s[3][NX], xo[3][NX];
+      const T dts[3] = {dtau_h, dtau_0, dtau_h};
+#pragma unroll
+      for (int j = 0; j < NU; ++j) us[0][j] = U[j], us[1][j] = U[j], us[2][j] = du[j] * P.h + U[j];  // :168-169
+#pragma unroll
+      for (int c = 0; c < NX; ++c) x0s[0][c] = xh[c], x0s[1][c] = xs[c], x0s[2][c] = xh[c];
+      W::template state_sweeps<3>(WL, us, x0s, dts, p, xo);
+      T phi[NU], dF[NUL], trig[1] = {T(0)};
+      backward(xo[0], trig, us[0], dtau_h, Gh, phi, dF);
+      finish(F_PLAIN, phi, dF, Fh);  // cgmres.hpp:88
+      backward(xo[1], trig, us[1], dtau_0, G0, phi, dF);
+      finish(F_RHS, phi, dF, bb);  // :91-96
+      backward(xo[2], trig, us[2], dtau_h, Gh, phi, dF);
+      finish(F_AX, phi, dF, ax0);  // :99 -> gmres.hpp:33
+      (void)xb, (void)tb;
+    } else if constexpr (!NONLIN) {
       // ---- the three sweeps in front of the solve, each ONE state scan + one costate scan (no serial sweep, no LDS)
       T x[NX], phi[NU], dF[NUL], uu[NU], trig[1] = {T(0)};
       W::state_scan(WL, U, xh, dtau_h, Gh, x);
@@ -548,7 +685,19 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(VLDS ?
       }
       if constexpr (!NONLIN) {
         T x[NX], phi[NU], dF[NUL], trig[1] = {T(0)};
-        W::state_scan(WL, u, xh, dtau_h, Gh, x);
+        if constexpr (SERIAL) {
+          T us[1][NU], x0s[1][NX], xo[1][NX];
+          const T dts[1] = {dtau_h};
+#pragma unroll
+          for (int j = 0; j < NU; ++j) us[0][j] = u[j];
+#pragma unroll
+          for (int c = 0; c < NX; ++c) x0s[0][c] = xh[c];
+          W::template state_sweeps<1>(WL, us, x0s, dts, p, xo);
+#pragma unroll
+          for (int c = 0; c < NX; ++c) x[c] = xo[0][c];
+        } else {
+          W::state_scan(WL, u, xh, dtau_h, Gh, x);
+        }
         CGM_STAMP(0, 3);
         backward(x, trig, u, dtau_h, Gh, phi, dF);
         finish(F_AX, phi, dF, out);
@@ -845,7 +994,10 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(VLDS ?
     }
     if (P.x_next) {  // plant step of the example main loop (<example>/main.cpp:71-73)
       T f[NX], tr[NC > 0 ? NC : 1];
-      M::dxdt(f, xs, unew, tr, mc);
+      if constexpr (SERIAL)
+        dxdt_p0(f, xs, unew);  // (the example's plant = the model's own state equation, p of stage 0)
+      else
+        M::dxdt(f, xs, unew, tr, mc);
 #pragma unroll
       for (int c = 0; c < NX; ++c) xs[c] = xs[c] + f[c] * P.dt;
       if (last && lane < NX) {

@@ -15,6 +15,9 @@
 //     g(s e_c) - q then loses eps*max(|q|, s|J|)/s = eps*max(1, |J|)-ish per entry instead of eps*|q| — with stiff cost
 //     weights (|q| ~ 1e6) the plain unit probe would put an ABSOLUTE error of 1e-10 on every Jacobian entry, which the
 //     recurrence multiplies by a costate of the size of q.  Scaling by a power of two is exact.
+//   * "wave" (tick_wave.hip.h, variant 4, only on request): WaveOps<UserDev<Model>> walks the state recurrence serially
+//     inside one wavefront (readlane of the stage's controls and parameters, the model's dxdt) and scans the costate
+//     recurrence as NX x NX affine maps built from the same stage_coeffs; dim_x <= 4, dim_u <= 6, dv <= 63, k_max <= 10.
 //     Whether dHdx / dHdu really ARE affine in the costate is checked once per process on the device
 //     (user_affinity_kernel: g(2 e_c) - g(0) against 2 (g(e_c) - g(0)) at two probe points); a model that fails runs on
 //     the lane mapping, which calls the user's functions as they are.
@@ -208,12 +211,13 @@ extern "C" int cgmres_hip_plugin_debug_lds_oob(void) {
     tuning[5] = mi.tol;                                                                                          \
   }                                                                                                              \
   /* a controller batch for this model on the requested / default mapping (wg when the sizes fit its LDS plan, */ \
-  /* lane otherwise), not yet initialised; nullptr for anything but fp64 or an unsupported explicit mapping      */ \
+  /* lane otherwise; wave only when asked for), not yet initialised; nullptr for anything but fp64 or an        */ \
+  /* unsupported explicit mapping                                                                               */ \
   cgmres_hip_ctx* cgmres_hip_plugin_make(const cgmres_hip_config* cfg) {                                         \
     if (cfg->dtype != CGMRES_HIP_F64) return nullptr;                                                            \
     int resolved = 0;                                                                                            \
     cgmres_hip_config c = *cfg;                                                                                  \
-    /* the wg mapping's generated split needs dHdx / dHdu affine in the costate: checked on the device */        \
+    /* the wg / wave mappings' generated split needs dHdx / dHdu affine in the costate: checked on the device */ \
     if (c.variant != 1 && !cgm::user_model_is_affine_in_costate<MODEL>(c.device)) {                              \
       if (c.variant != 0) {                                                                                      \
         cgm::fail(CGMRES_HIP_EINVAL, "user model: dHdx/dHdu are not affine in the costate: lane mapping only");  \

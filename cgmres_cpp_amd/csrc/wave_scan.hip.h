@@ -205,6 +205,52 @@ __device__ __forceinline__ void scan_aff2_vec(T* c, const Aff2Levels<T>& lv) {
   aff2_step_vec<5>(c, lv.d[5]);
 }
 
+// N x N affine maps  y -> y + D y + c  (D row-major, N*N entries): the generalisation of scan_aff2 with the same partner
+// pattern and zero fill, for the costate recurrences of user models (WaveOps<UserDev<Model>>).  Step t composes the
+// lane's map after its partner's:  (D, c) o (Dp, cp) = (D + Dp + D Dp,  c + cp + D cp).  After the call c holds the
+// composed offset of the lane's prefix (= the value of the recurrence started from 0); D is destroyed.
+template <int N, int STEP, class T>
+__device__ __forceinline__ void affn_step(T* D, T* c) {
+  T p[N], n[N];
+#pragma unroll
+  for (int r = 0; r < N; ++r) p[r] = scan_partner<STEP>(c[r]);
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+    T a = c[r] + p[r];
+#pragma unroll
+    for (int k = 0; k < N; ++k) a = fma_t(D[N * r + k], p[k], a);
+    n[r] = a;
+  }
+#pragma unroll
+  for (int r = 0; r < N; ++r) c[r] = n[r];
+  if constexpr (STEP < 5) {  // (the last step needs no composed matrix)
+    T Q[N * N], M[N * N];
+#pragma unroll
+    for (int e = 0; e < N * N; ++e) Q[e] = scan_partner<STEP>(D[e]);
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) {
+        T a = D[N * r + k] + Q[N * r + k];
+#pragma unroll
+        for (int m = 0; m < N; ++m) a = fma_t(D[N * r + m], Q[N * m + k], a);
+        M[N * r + k] = a;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < N * N; ++e) D[e] = M[e];
+  }
+}
+template <int N, class T>
+__device__ __forceinline__ void scan_affn(T* D, T* c) {
+  affn_step<N, 0>(D, c);
+  affn_step<N, 1>(D, c);
+  affn_step<N, 2>(D, c);
+  affn_step<N, 3>(D, c);
+  affn_step<N, 4>(D, c);
+  affn_step<N, 5>(D, c);
+}
+
 // ---- 4 x 4 affine maps with the SAME matrix in every element (linear time-invariant state / costate equations) ---------
 // y' = y + D y + c_i.  The scan of such elements composes only matrices that are POWERS of M = I + D: step t of an in-row
 // step uses M^(2^t), the two cross-row steps M^((i & 15) + 1) and M^((i & 31) + 1) — all found in one table

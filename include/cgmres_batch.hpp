@@ -18,9 +18,12 @@ class CgmresBatch {
  public:
   static constexpr uint16_t dim_x = Model::dim_x, dim_u = Model::dim_u, dim_p = Model::dim_p, dv = Model::dv;
 
-  explicit CgmresBatch(int32_t batch, int32_t device = 0, void* hip_stream = nullptr) : batch_(batch) {
+  // variant: the kernel mapping of cgmres_hip_config::variant (0 = the library's choice, 4 = "wave", ...)
+  explicit CgmresBatch(int32_t batch, int32_t device = 0, void* hip_stream = nullptr, int32_t variant = 0)
+      : batch_(batch) {
     cgmres_hip_config cfg = cgmres_detail::config_for<Model>(batch, device);
     cfg.stream = hip_stream;
+    cfg.variant = variant;
     cgmres_detail::check(cgmres_hip_create(&cfg, &handle_), "create");
   }
   ~CgmresBatch() {

@@ -99,7 +99,9 @@ typedef struct cgmres_hip_config {
   int32_t variant;     /* kernel mapping: 0 = library's choice, 1 = "lane", 2 = "wg" (one workgroup per CU: everything
                           of 16 instances in LDS), 3 = "wg-lean" (half the LDS, two workgroups per CU),
                           4 = "wave" (one wavefront per controller, horizon recurrences as wave scans: the latency
-                          mapping for batches smaller than the GPU); get_config returns the resolved value */
+                          mapping for batches smaller than the GPU; user models take it only when asked for
+                          explicitly, within dim_x <= 4, dim_u <= 6, dv <= 63, k_max <= 10); get_config returns the
+                          resolved value */
   int32_t flags;       /* CGMRES_HIP_FLAG_* (0 = library defaults) */
   int32_t reserved;    /* 0 */
   double tol;          /* Model::tol */
@@ -127,7 +129,9 @@ int cgmres_hip_model_probe(int32_t model_id, int32_t device, const double* x, co
  * cgmres_cpp_amd/plugin.py (hipcc, gfx950).  *model_id receives an id >= CGMRES_HIP_MODEL_USER_BASE that every
  * other entry point accepts; such models run in fp64, on the "wg" mapping when their sizes fit its LDS plan
  * (the affine costate split is generated from the user's own dHdx / dHdu, csrc/user_model.hip.h) and on the "lane"
- * mapping otherwise.  Registering the same path twice returns the same id.  This is what a `Cgmres<Model>` facade binds for a Model that is not in the registry. */
+ * mapping otherwise.  An explicit variant = 4 runs them on the "wave" mapping (serial state sweep inside the wave,
+ * costate recurrence as a scan of dim_x x dim_x affine maps) where the wg mapping serves the sizes and dim_x <= 4,
+ * dim_u <= 6, dv <= 63, k_max <= 10; outside those limits it fails with CGMRES_HIP_EINVAL.  Registering the same path twice returns the same id.  This is what a `Cgmres<Model>` facade binds for a Model that is not in the registry. */
 int cgmres_hip_register_model(const char* plugin_path, int32_t* model_id);
 /* ---- stand-alone Gmres with a caller-supplied operator: class Gmres, reference include/gmres.hpp:8-129 ------------ */
 /* Registers a device OPERATOR: `plugin_path` is a shared object generated by cgmres_cpp_amd/plugin.py
