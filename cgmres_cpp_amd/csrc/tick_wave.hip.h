@@ -208,7 +208,7 @@ struct WaveOps<MsdDev<T>> : std::true_type {
 // coefficients UserDev::stage_coeffs generates by probing the user's dHdx / dHdu (checked on the device,
 // user_affinity_kernel): lambda(s) = (I + dtau J(s)^T) lambda(s+1) + dtau q(s) — one scan of NX x NX affine maps on
 // the mirrored lanes (scan_affn), and dF(s) = B(s)^T lambda(s+1) on the lane of stage s.
-// Limits (CtxWg::wave_supported): NX <= kUserWaveMaxNx — the scan keeps a map and its DPP partner (2 NX^2 + 2 NX
+// Limits (WgTraits::wave_supported, wg_plan.hip.h): NX <= kUserWaveMaxNx — the scan keeps a map and its DPP partner (2 NX^2 + 2 NX
 // doubles) next to the register-resident Krylov basis; NU <= kUserWaveMaxNu (the basis is (k_max + 1) NU doubles per lane).
 constexpr int kUserWaveMaxNx = 4, kUserWaveMaxNu = 6;
 template <class Model>

@@ -62,7 +62,7 @@ struct WgParams {
   int wave_dbg;   // wave mapping (tick_wave.hip.h): 1 = Newton with fresh sin/cos, 2 = serial state sweep in every mat-vec
   int cs_chunks;  // chunks of the two-pass costate sweep (WgCtx::sweep_costate_2pass): 3 or 4, what the LDS budget allows
   // row-parallel Newton kernel (WgCtx::NWT = 1): byte offsets, from the start of the workgroup's LDS, of the arrays that hold
-  // the tick's base trajectory during the Arnoldi loop (ctx_wg.hip.h places them: in the stage table and in the scratch of
+  // the tick's base trajectory during the Arnoldi loop (plan_wg, wg_plan.hip.h, places them: in the stage table and in the scratch of
   // the chunk-parallel costate sweep, both idle then, and behind everything else where those do not suffice)
   int base_off[8];
    // Lp/Pp/Hp: odd LDS row pitches (Hp: the COMPACT Hessenberg, column k = rows 0..k at offset k(k+1)/2; h(k+1,k) of the
@@ -180,13 +180,6 @@ struct WgLds {
     if constexpr (TABX != 0) return size_t(dv + TAB_PAD) * (NSTG * IPW + TABX);
     return size_t(dv + TAB_PAD) * NSTG * IPW;
   }
-  static __host__ __device__ size_t count_T(int dv, int kmax, int Lp, int Pp, int Hp, int plan = PLAN_FULL) {
-    const int k1 = kmax + 1;
-    const int rows = plan == PLAN_FULL ? 3 : (plan == PLAN_FH_HBM ? 2 : 1);
-    return size_t(rows) * IPW * Lp + tab_count(dv) + (plan == PLAN_LEAN ? 0 : size_t(IPW) * Pp) + size_t(IPW) * Hp +
-           size_t(IPW) * k1 + size_t(IPW) * 3 * kmax + size_t(IPW) + size_t(plan == PLAN_LEAN ? 4 : 5) * M::NX * IPW +
-           (plan == PLAN_LEAN ? size_t(M::NU) * IPW : 0);
-  }
   // chunk-parallel costate sweep (WgCtx::sweep_costate_par): dF of the homogeneous lanes for the 3*(dv/4) stages of
   // chunks 1..3, then four boundary records per instance (k = 0..3): [NX*NX transfer matrix, row-major][NX vector]
   // [pad], read with 16-byte loads — SCAN_REC doubles apart so that the 16 instances of a read fall into distinct banks
@@ -200,11 +193,25 @@ struct WgLds {
   static __host__ __device__ size_t scan2_count(int chunks) {
     return size_t(IPW) * M::NX + size_t(chunks - 2) * IPW * SCAN_REC;
   }
-  // scan_T: scalars of costate-sweep scratch behind the small arrays (scan_count(dv), scan2_count(chunks) or 0)
-  static __host__ __device__ size_t bytes(int dv, int kmax, int Lp, int Pp, int Hp, int plan = PLAN_FULL, size_t scan_T = 0) {
-    return count_T(dv, kmax, Lp, Pp, Hp, plan) * sizeof(T) + 5 * IPW * sizeof(int) + 16 + (scan_T ? scan_T * sizeof(T) + 16 : 0);
+  // The constructor below is the one description of the carve-up: the host sizes the allocation by running it on a
+  // made-up base address (extent) for the TABX the kernel is instantiated with.
+  struct Extent {
+    size_t tab_off, status_end, scan_off;  // bytes from the base: stage table, end of the status words, aligned `scan`
+  };
+  static Extent extent(int dv, int kmax, int Lp, int Pp, int Hp, int plan) {
+    WgParams<T> P{};
+    P.dv = dv, P.kmax = kmax, P.Lp = Lp, P.Pp = Pp, P.Hp = Hp;
+    unsigned char* const base = reinterpret_cast<unsigned char*>(size_t(1) << 30);  // (never dereferenced)
+    const WgLds S(base, P, plan);
+    return {size_t(reinterpret_cast<unsigned char*>(S.R) - base), size_t(reinterpret_cast<unsigned char*>(S.binst + IPW) - base),
+            size_t(reinterpret_cast<unsigned char*>(S.scan) - base)};
   }
-  __device__ __forceinline__ WgLds(unsigned char* base, const WgParams<T>& P, int plan) {
+  // bytes up to and including the status words; the + 16 absorbs the 16-byte alignment of `scan`, behind which the planner
+  // (wg_plan.hip.h) adds the costate scratch
+  static size_t bytes(int dv, int kmax, int Lp, int Pp, int Hp, int plan = PLAN_FULL) {
+    return extent(dv, kmax, Lp, Pp, Hp, plan).status_end + 16;
+  }
+  __host__ __device__ __forceinline__ WgLds(unsigned char* base, const WgParams<T>& P, int plan) {
     T* q = reinterpret_cast<T*>(base);
     lds0 = base;
     const int k1 = P.kmax + 1;
@@ -1027,7 +1034,7 @@ struct WgCtx {
     // Three register sets, three stages per trip: the operands of stage t-2 are requested while stage t computes
     // (two LDS latencies of slack).  q/o sit on stage s-4 of the trip that starts with stage s: every access is
     // pointer + non-negative immediate.  Below stage 0 the look-ahead reads words of the preceding LDS arrays
-    // (at most 3 stages = 3*STEP scalars — the `post` tail below — which CtxWg::lookahead_fits guarantees to lie
+    // (at most 3 stages = 3*STEP scalars — the `post` tail below — which WgTraits::lookahead_fits (wg_plan.hip.h) guarantees to lie
     // inside the row arrays in front of the table), never used.  LDS accesses outside the workgroup's allocation
     // FAULT on this platform (aperture violation): -DCGM_DEBUG_LDS checks every address here.
 #ifdef CGM_DEBUG_LDS
@@ -1531,7 +1538,7 @@ struct WgCtx {
   mutable bool row_moved = true;  // the published direction changed at least one control of this row (publish_direction)
   // During the Arnoldi loop the base lives in LDS — in the stage table, which only the preamble's state sweeps use, in
   // the scratch of the serial-sweep kernel's costate scan, which this kernel does not use at all, and behind everything
-  // else where those two are too small (ctx_wg places the arrays: WgParams::base_off) — as pairs [q / 2][thread] per
+  // else where those two are too small (plan_wg places the arrays: WgParams::base_off) — as pairs [q / 2][thread] per
   // array: every lane reads back
   // exactly what it wrote (no barrier), 16 bytes per access, conflict-free.  Call after the preamble's last barrier.
   __device__ __forceinline__ Pair* base_pairs(int k, int thread) const {

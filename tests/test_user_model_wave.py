@@ -109,7 +109,7 @@ def test_wave_four_state_model_teacher_forced(tmp_path, dv):
     """(c) dim_x = 4 (a 4 x 4 affine costate scan), against the oracle's generic controller, teacher-forced: every tick
     starts from the oracle's controller and plant state, stays within the single-tick bound and runs the oracle's
     number of Arnoldi iterations.  dv covers every remainder across the 16-lane DPP rows and the 63-lane edge; below
-    dv = 24 the wg context of this model cannot be created (CtxWg::lookahead_fits), so neither can the wave one."""
+    dv = 24 the wg context of this model cannot be created (WgTraits::lookahead_fits, wg_plan.hip.h), so neither can the wave one."""
     mid = plugin.register(_chain4_plugin("Chain4Model", "chain4_dbg", ("-DCGM_DEBUG_LDS",)))
     Bn, ticks, kmax, tol = 20, 12, 5, 1e-9
     u_ref, x_ref, k_ref, state = _user_oracle(tmp_path, CHAIN4, "Chain4Model", Bn, ticks, dv, kmax, tol, with_state=True)

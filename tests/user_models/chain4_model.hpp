@@ -2,7 +2,7 @@
 // two masses on a chain of springs, the outer one hardening (cubic), ONE unconstrained input on the first mass, a
 // reference p[0] for the first position.  dim_x = 4 with dim_u = 1 is the shape that stresses the wg mapping's LDS plan
 // for plugins: 4*4 + 1*4 + 4 = 24 stage coefficients per (stage, instance) against a row of only dv controls
-// (CtxWg::lookahead_fits), so short horizons must fall back to the lane mapping.
+// (WgTraits::lookahead_fits, wg_plan.hip.h), so short horizons must fall back to the lane mapping.
 // Chain4T<1> is the same plant with STIFF cost weights (1e5 on the position error, 1e-2 on the input): the
 // costate-free part q of dH/dx is then five orders of magnitude above the Jacobian entries the plugin glue derives by
 // differencing (csrc/user_model.hip.h: scaled probe costates).
