@@ -325,6 +325,11 @@ int cgmres_hip_create(const cgmres_hip_config* cfg, cgmres_hip_handle* out) {
   if (len >= 32768 || len * (cfg->k_max + 1) >= 65536)
     return fail(CGMRES_HIP_EINVAL, "dim_u*dv = %ld with k_max = %d exceeds the reference's 16-bit index range", len, cfg->k_max);
   if (!(cfg->h > 0) || !(cfg->dt > 0) || !(cfg->tol >= 0)) return fail(CGMRES_HIP_EINVAL, "h, dt must be > 0 and tol >= 0");
+  // a NaN / Inf tuning constant would only show as NaN controls many ticks later (1 - zeta*h, 1/h, dtau(t) scale every residual)
+  for (double v : {cfg->dt, cfg->h, cfg->zeta, cfg->Tf, cfg->alpha})
+    if (!std::isfinite(v))
+      return fail(CGMRES_HIP_EINVAL, "dt, h, zeta, Tf, alpha must be finite (got %g, %g, %g, %g, %g)", cfg->dt, cfg->h, cfg->zeta,
+                  cfg->Tf, cfg->alpha);
   if (cfg->variant < 0 || cfg->variant > 4) return fail(CGMRES_HIP_EINVAL, "unknown variant %d", cfg->variant);
   if (cfg->flags & ~(CGMRES_HIP_FLAG_SERIAL_COSTATE | CGMRES_HIP_FLAG_IPW8 | CGMRES_HIP_FLAG_NO_BINNING | CGMRES_HIP_FLAG_TWO_PASS_COSTATE |
                      CGMRES_HIP_FLAG_NO_WAVE | CGMRES_HIP_FLAG_WAVE_FRESH_TRIG | CGMRES_HIP_FLAG_WAVE_SERIAL_SWEEPS |

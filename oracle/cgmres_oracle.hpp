@@ -12,7 +12,7 @@
 //
 // Differences from the reference that are deliberate and documented:
 //   * dUdt(0) = 0 (the reference reads an uninitialised heap array on the first tick);
-//   * dv / k_max / tol are run-time values;
+//   * dv / k_max / tol and the tuning constants dt / h / zeta / Tf / alpha are run-time values;
 //   * the executed Arnoldi count and exit reason are recorded (the reference drops them).
 #pragma once
 #include <cfloat>
@@ -36,14 +36,16 @@ class Controller {
  public:
   static constexpr int nx = Model::dim_x, nu = Model::dim_u, np = Model::dim_p;
 
-  Controller(int dv, int kmax, double tol)
-      : dv_(dv), kmax_(kmax), len_(nu * dv), tol_(T(tol)), tun_(Model::tuning()),
+  // tun: the model's shipped constants unless the caller sets its own (run-time fields of cgmres_hip_config)
+  Controller(int dv, int kmax, double tol, Tuning tun = Model::tuning())
+      : dv_(dv), kmax_(kmax), len_(nu * dv), tol_(T(tol)), tun_(tun),
         U_(len_, T(0)), dUdt_(len_, T(0)), Fh_(len_, T(0)), xh_(nx, T(0)), ptau_(np * (dv + 1) + 1, T(0)),
         V_(size_t(len_) * (kmax + 1), T(0)), H_(size_t(kmax + 1) * (kmax + 1), T(0)), rho_(kmax + 1, T(0)),
         g_(3 * kmax, T(0)), scratch_(len_, T(0)), xtau_(nx * (dv + 1)), ltau_(nx * (dv + 1)), b_(len_, T(0)),
         ub_(len_, T(0)) {}
 
   int dv() const { return dv_; }
+  const Tuning& tuning() const { return tun_; }
   int kmax() const { return kmax_; }
   int len() const { return len_; }
 

@@ -26,10 +26,11 @@ template <class Model, class T>
 struct Impl : OrcBase {
   oracle::Controller<Model, T> c;
   static constexpr int nx = Model::dim_x, nu = Model::dim_u, np = Model::dim_p;
-  Impl(int dv, int kmax, double tol, int dtype) : c(dv, kmax, tol) {
+  Impl(int dv, int kmax, double tol, int dtype, const double* tn)
+      : c(dv, kmax, tol, tn ? oracle::Tuning{tn[0], tn[1], tn[2], tn[3], tn[4]} : Model::tuning()) {
     int d[7] = {nx, nu, np, dv, kmax, nu * dv, dtype};
     std::memcpy(dims, d, sizeof d);
-    auto tu = Model::tuning();
+    const auto tu = c.tuning();
     double q[5] = {tu.dt, tu.h, tu.zeta, tu.Tf, tu.alpha};
     std::memcpy(tun, q, sizeof q);
   }
@@ -76,7 +77,7 @@ struct Impl : OrcBase {
   // cgmres.hpp:83-96 without the solve
   void prepare(double* b, const double* x) override {
     auto xv = in<T>(x, nx);
-    const auto tu = Model::tuning();
+    const auto tu = c.tuning();
     const T h = T(tu.h), zeta = T(tu.zeta);
     T* xh = c.xh().data();
     Model::dxdt(xh, xv.data(), &c.U()[0], &c.ptau()[0]);
@@ -125,22 +126,23 @@ struct Impl : OrcBase {
 };
 
 template <class T>
-OrcBase* make(int model, int dv, int kmax, double tol, int dtype) {
+OrcBase* make(int model, int dv, int kmax, double tol, int dtype, const double* tun) {
   switch (model) {
     case oracle::kPendulum:
-      return new Impl<oracle::Pendulum<T>, T>(dv, kmax, tol < 0 ? oracle::Pendulum<T>::tol : tol, dtype);
+      return new Impl<oracle::Pendulum<T>, T>(dv, kmax, tol < 0 ? oracle::Pendulum<T>::tol : tol, dtype, tun);
     case oracle::kMassSpringDamper:
       return new Impl<oracle::MassSpringDamper<T>, T>(dv, kmax, tol < 0 ? oracle::MassSpringDamper<T>::tol : tol,
-                                                      dtype);
+                                                      dtype, tun);
     case oracle::kSemiactiveDamper:
       return new Impl<oracle::SemiactiveDamper<T>, T>(dv, kmax, tol < 0 ? oracle::SemiactiveDamper<T>::tol : tol,
-                                                      dtype);
+                                                      dtype, tun);
   }
   return nullptr;
 }
 
 }  // namespace
 
-OrcBase* orc_factory(int model, int dv, int kmax, double tol, int dtype) {
-  return dtype == 1 ? make<float>(model, dv, kmax, tol, 1) : make<double>(model, dv, kmax, tol, 0);
+// tun = NULL: the model's shipped tuning (the constructor's default, so orc_create computes what it always did)
+OrcBase* orc_factory(int model, int dv, int kmax, double tol, int dtype, const double* tun) {
+  return dtype == 1 ? make<float>(model, dv, kmax, tol, 1, tun) : make<double>(model, dv, kmax, tol, 0, tun);
 }

@@ -24,8 +24,12 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 
 
+TUNING_FIELDS = ("dt", "h", "zeta", "Tf", "alpha")
+
+
 def build(ref=True, quiet=True):
-    """Compile liboracle.so (always) and _ref/libref.so (when the reference tree is mounted)."""
+    """Compile liboracle.so (always) and _ref/libref.so (when the reference tree is mounted).  The make rules depend on
+    the sources: an up-to-date library is left alone, one left from an older checkout is rebuilt."""
     targets = ["oracle"]
     if ref and os.path.isdir(REFERENCE_ROOT):
         targets.append("ref")
@@ -37,6 +41,11 @@ def _load(path):
     lib = C.CDLL(path)
     lib.orc_create.restype = C.c_void_p
     lib.orc_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]
+    if not hasattr(lib, "orc_create_tuned"):
+        raise OSError(f"{path} predates orc_create_tuned (oracle/orc_api.h): rebuild it with `make -C {HERE} "
+                      f"{'oracle' if path == ORACLE_SO else 'ref'}`")
+    lib.orc_create_tuned.restype = C.c_void_p
+    lib.orc_create_tuned.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _dp]
     lib.orc_destroy.argtypes = [C.c_void_p]
     lib.orc_dims.argtypes = [C.c_void_p, _ip]
     lib.orc_tuning.argtypes = [C.c_void_p, _dp]
@@ -64,6 +73,13 @@ _libs = {}
 def lib(which="oracle"):
     if which not in _libs:
         path = ORACLE_SO if which == "oracle" else REF_SO
+        if os.path.exists(path) and (which == "oracle" or os.path.isdir(REFERENCE_ROOT)):
+            # a library left from an older checkout would lack entry points (or compute the older thing): let make decide,
+            # once per process, before the first load (a no-op when it is up to date)
+            try:
+                build(ref=which != "oracle")
+            except FileNotFoundError:
+                pass  # no make on this machine: _load() still refuses a library that lacks an entry point
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path} not built (python -c 'import oracle.orc as o; o.build()')")
         _libs[which] = _load(path)
@@ -89,11 +105,20 @@ class Controller:
     """One controller instance of either checker library; method names follow the reference
     (include/cgmres.hpp: set_ptau / init_u0 / init_u0_newton / control)."""
 
-    def __init__(self, model, dv, kmax, tol=-1.0, dtype="f64", which="oracle"):
+    def __init__(self, model, dv, kmax, tol=-1.0, dtype="f64", which="oracle", tuning=None):
+        """tuning: None = the model's shipped constants (orc_create), else a dict with all of dt, h, zeta, Tf, alpha
+        (orc_create_tuned)."""
         self._lib = lib(which)
-        self._h = self._lib.orc_create(model, dv, kmax, float(tol), 1 if dtype == "f32" else 0)
+        if tuning is None:
+            self._h = self._lib.orc_create(model, dv, kmax, float(tol), 1 if dtype == "f32" else 0)
+        else:
+            if sorted(tuning) != sorted(TUNING_FIELDS):
+                raise TypeError(f"tuning must give exactly {TUNING_FIELDS}, got {sorted(tuning)}")
+            tun = np.array([float(tuning[k]) for k in TUNING_FIELDS])
+            self._h = self._lib.orc_create_tuned(model, dv, kmax, float(tol), 1 if dtype == "f32" else 0, _p(tun))
         if not self._h:
-            raise ValueError(f"{which}: combination not built: model={model} dv={dv} kmax={kmax} tol={tol}")
+            raise ValueError(f"{which}: combination not built: model={model} dv={dv} kmax={kmax} tol={tol} "
+                             f"tuning={tuning}")
         d = (C.c_int * 7)()
         self._lib.orc_dims(self._h, d)
         self.dim_x, self.dim_u, self.dim_p, self.dv, self.kmax, self.len, _ = list(d)

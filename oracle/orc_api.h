@@ -15,6 +15,10 @@ extern "C" {
  * tol < 0 selects the model's shipped tol (1e-6).  Returns NULL when the combination is not built
  * (libref only instantiates the table in oracle/ref_harness.cpp). */
 void* orc_create(int model, int dv, int kmax, double tol, int dtype);
+/* The same with the tuning constants given at run time: tun[0..4] = dt, h, zeta, Tf, alpha (the run-time fields of
+ * cgmres_hip_config).  liboracle takes any values; libref returns NULL except for the sets and sizes compiled into
+ * oracle/ref_harness.cpp (TUNED_CASES of oracle/ref_records.py), matched on all five values. */
+void* orc_create_tuned(int model, int dv, int kmax, double tol, int dtype, const double tun[5]);
 void orc_destroy(void* c);
 /* out[0..6] = dim_x, dim_u, dim_p, dv, kmax, len, dtype */
 void orc_dims(void* c, int* out);

@@ -29,13 +29,18 @@ struct OrcBase {
   virtual void plant(double*, const double*, const double*) = 0;
 };
 
-OrcBase* orc_factory(int model, int dv, int kmax, double tol, int dtype);
+// tun: NULL = the model's shipped tuning, else dt, h, zeta, Tf, alpha
+OrcBase* orc_factory(int model, int dv, int kmax, double tol, int dtype, const double* tun);
 
 #ifdef ORC_DEFINE_CAPI
 extern "C" {
 void* orc_create(int model, int dv, int kmax, double tol, int dtype) {
   if (dv < 1 || kmax < 1) return nullptr;
-  return orc_factory(model, dv, kmax, tol, dtype);
+  return orc_factory(model, dv, kmax, tol, dtype, nullptr);
+}
+void* orc_create_tuned(int model, int dv, int kmax, double tol, int dtype, const double tun[5]) {
+  if (dv < 1 || kmax < 1 || !tun) return nullptr;
+  return orc_factory(model, dv, kmax, tol, dtype, tun);
 }
 void orc_destroy(void* c) { delete static_cast<OrcBase*>(c); }
 void orc_dims(void* c, int* o) { std::memcpy(o, static_cast<OrcBase*>(c)->dims, 7 * sizeof(int)); }

@@ -5,6 +5,7 @@
 // No reference source is copied: this file only #includes it.  Techniques:
 //   * white-box access: libc headers first, then `#define private public` around the includes;
 //   * BASELINE sizes: a subclass of the example's Model shadows dv / k_max / tol;
+//   * run-time tuning (orc_create_tuned): a tag struct makes the same subclass shadow dt / h / zeta / Tf / alpha too;
 //   * Arnoldi count: the subclass wraps Model::dHdu and counts calls (one F-eval = dv calls);
 //   * deterministic first tick: dUdt (uninitialised in the reference ctor, cgmres.hpp:14) is zeroed;
 //   * fp32 build (-DREF_F32): `#define double float` around the reference includes.
@@ -56,9 +57,29 @@ typedef double real;  // float in the REF_F32 build (macro still active here)
 
 namespace REF_NS {
 
-// Size/tol override + dHdu call counter, without editing the example's Model.
-template <class M, int DV, int KM, int ZERO_TOL>
-struct Sized : M {
+// Tuning tags.  Shipped leaves the example's own constants visible; any other tag shadows all five, the way Sized
+// shadows dv / k_max / tol.  The values are those of TUNING_SETS in oracle/ref_records.py (tests/tuning_cases.py).
+struct Shipped {};
+struct TunFast {
+  static constexpr double dt = 5e-4, h = 1e-3, zeta = 1500.0, Tf = 0.25, alpha = 4.0;
+};
+struct TunLong {
+  static constexpr double dt = 1e-3, h = 4e-3, zeta = 125.0, Tf = 1.5, alpha = 1.0;
+};
+struct TunMid {
+  static constexpr double dt = 1e-3, h = 3e-3, zeta = 400.0, Tf = 1.0, alpha = 3.0;
+};
+template <class M, class Tag>
+struct Tuned : M {
+  static constexpr real dt = real(Tag::dt), h = real(Tag::h), zeta = real(Tag::zeta), Tf = real(Tag::Tf),
+                        alpha = real(Tag::alpha);
+};
+template <class M>
+struct Tuned<M, Shipped> : M {};
+
+// Size/tol/tuning override + dHdu call counter, without editing the example's Model.
+template <class M, int DV, int KM, int ZERO_TOL, class Tag = Shipped>
+struct Sized : Tuned<M, Tag> {
   static constexpr uint16_t dv = DV;
   static constexpr uint16_t k_max = KM;
   static constexpr real tol = ZERO_TOL ? real(0.0) : real(1e-6);
@@ -216,10 +237,45 @@ OrcBase* make(int model, int dv, int km, double tol, int dtype) {
   return nullptr;
 }
 
+// Tuned table: every set at the tiny size, `long` at (50, 10); shipped tol only.  A request is served only when all
+// five values equal a tag's.
+template <class Tag>
+bool is_set(const double* t) {
+  return t[0] == Tag::dt && t[1] == Tag::h && t[2] == Tag::zeta && t[3] == Tag::Tf && t[4] == Tag::alpha;
+}
+
+template <class M, class Sim>
+OrcBase* pick_tuned(int dv, int km, int dtype, const double* t) {
+  if (dv == 8 && km == 3) {
+    if (is_set<TunFast>(t)) return new RefImpl<Sized<M, 8, 3, 0, TunFast>, Sim>(dtype);
+    if (is_set<TunLong>(t)) return new RefImpl<Sized<M, 8, 3, 0, TunLong>, Sim>(dtype);
+    if (is_set<TunMid>(t)) return new RefImpl<Sized<M, 8, 3, 0, TunMid>, Sim>(dtype);
+  }
+  if (dv == 50 && km == 10 && is_set<TunLong>(t)) return new RefImpl<Sized<M, 50, 10, 0, TunLong>, Sim>(dtype);
+  return nullptr;
+}
+
+OrcBase* make_tuned(int model, int dv, int km, double tol, int dtype, const double* t) {
+  if (!(tol < 0 || tol == 1e-6)) return nullptr;
+  switch (model) {
+    case 0:
+      return pick_tuned<pend::Model, pend::Simulator>(dv, km, dtype, t);
+    case 1:
+      return pick_tuned<msd::Model, msd::Simulator>(dv, km, dtype, t);
+    case 2:
+      return pick_tuned<semi::Model, semi::Simulator>(dv, km, dtype, t);
+  }
+  return nullptr;
+}
+
 }  // namespace REF_NS
 
 #ifdef REF_F32
-OrcBase* ref_make_f32(int model, int dv, int km, double tol) { return ref32::make(model, dv, km, tol, 1); }
+OrcBase* ref_make_f32(int model, int dv, int km, double tol, const double* tun) {
+  return tun ? ref32::make_tuned(model, dv, km, tol, 1, tun) : ref32::make(model, dv, km, tol, 1);
+}
 #else
-OrcBase* ref_make_f64(int model, int dv, int km, double tol) { return ref64::make(model, dv, km, tol, 0); }
+OrcBase* ref_make_f64(int model, int dv, int km, double tol, const double* tun) {
+  return tun ? ref64::make_tuned(model, dv, km, tol, 0, tun) : ref64::make(model, dv, km, tol, 0);
+}
 #endif
