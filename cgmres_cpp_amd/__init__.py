@@ -36,7 +36,7 @@ SYMBOLS = [
     "cgmres_hip_get_time", "cgmres_hip_get_state", "cgmres_hip_set_state", "cgmres_hip_get_status",
     "cgmres_hip_get_krylov", "cgmres_hip_F_func", "cgmres_hip_prepare", "cgmres_hip_Ax_func", "cgmres_hip_gmres",
     "cgmres_hip_timer_start", "cgmres_hip_timer_stop", "cgmres_hip_malloc", "cgmres_hip_free",
-    "cgmres_hip_memcpy_h2d", "cgmres_hip_memcpy_d2h",
+    "cgmres_hip_memcpy_h2d", "cgmres_hip_memcpy_d2h", "cgmres_hip_state_rows",
 ]
 
 
@@ -110,6 +110,8 @@ def load():
     lib.cgmres_hip_free.argtypes = [vp, vp]
     lib.cgmres_hip_memcpy_h2d.argtypes = [vp, vp, vp, C.c_uint64]
     lib.cgmres_hip_memcpy_d2h.argtypes = [vp, vp, vp, C.c_uint64]
+    if hasattr(lib, "cgmres_hip_state_rows"):  # (absent from A/B builds of older sources, tools/ab_build.py)
+        lib.cgmres_hip_state_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
     _lib = lib
     return lib
 
@@ -400,6 +402,14 @@ class CgmresBatch:
         Ua = self._host(U, (self.batch, self.len))[0] if U is not None else None
         da = self._host(dUdt, (self.batch, self.len))[0] if dUdt is not None else None
         _check(load().cgmres_hip_set_state(self._h, float(t), _ptr(Ua), _ptr(da)))
+
+    def state_rows(self):
+        """(U, dUdt, pitch): device addresses of the controller state as the kernels keep it, [batch][pitch] scalars with
+        pitch >= dim_u*dv (the words behind dim_u*dv of a row are pads no kernel reads or writes); None for a mapping
+        that keeps its state in another form."""
+        U, d, pitch = C.c_void_p(), C.c_void_p(), C.c_int32()
+        _check(load().cgmres_hip_state_rows(self._h, C.byref(U), C.byref(d), C.byref(pitch)))
+        return (U.value, d.value, pitch.value) if U.value else None
 
     def get_status(self):
         n = np.empty(self.batch, dtype=np.int32)

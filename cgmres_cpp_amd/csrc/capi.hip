@@ -430,6 +430,11 @@ int cgmres_hip_set_state(cgmres_hip_handle h, double t, const void* U, const voi
   NEED(h);
   return h->set_state(t, U, dUdt);
 }
+int cgmres_hip_state_rows(cgmres_hip_handle h, void** U, void** dUdt, int32_t* pitch) {
+  NEED(h);
+  if (!U || !dUdt || !pitch) return fail(CGMRES_HIP_EINVAL, "state_rows: null pointer");
+  return h->state_rows(U, dUdt, pitch);
+}
 int cgmres_hip_get_status(cgmres_hip_handle h, int32_t* n_ax, int32_t* reason) {
   NEED(h);
   return h->get_status(n_ax, reason);

@@ -105,6 +105,10 @@ struct cgmres_hip_ctx {
   virtual double time() const = 0;
   virtual int get_state(double*, void*, void*) = 0;
   virtual int set_state(double, const void*, const void*) = 0;
+  virtual int state_rows(void** U, void** dUdt, int32_t* pitch) {  // mappings without instance-major state rows: none
+    *U = nullptr, *dUdt = nullptr, *pitch = 0;
+    return 0;
+  }
   virtual int get_status(int32_t*, int32_t*) = 0;
   virtual int get_krylov(void*, void*, void*, void*) = 0;
   virtual int hook_F(void*, const void*, const void*, double) = 0;

@@ -3,6 +3,7 @@
 #pragma once
 #include <vector>
 #include "ctx_common.hip.h"
+#include "stage_own.hip.h"
 #include "tick_wave.hip.h"
 #include "tick_wg.hip.h"
 #include "wg_plan.hip.h"
@@ -41,6 +42,10 @@ struct CtxWg final : cgmres_hip_ctx {
     if (pin_x) (void)hipHostFree(pin_x);
     if (pin_u) (void)hipHostFree(pin_u);
   }
+  // The Krylov rows in HBM follow the ownership of the kernel that wrote them last: the row-parallel Newton kernel keeps
+  // its vectors by stage (stage_own.hip.h), every other kernel of this context — the white-box hooks included — by rows
+  // (WgCtx::load_vec).  get_krylov un-permutes accordingly.
+  bool v_by_stage = false;
   int* perm_dev = nullptr;   // placement of the next fused launch (bin_by_count_kernel)
   bool have_counts = false;  // n_ax holds the counts of a finished tick
   using Tr = WgTraits<M, T>;
@@ -102,7 +107,7 @@ struct CtxWg final : cgmres_hip_ctx {
     P.B = cfg.batch, P.dv = cfg.dv, P.kmax = cfg.k_max, P.L = L, P.fh_hbm = plan.fh_hbm, P.lds_bytes = int(plan.lds_bytes);
     P.cs_chunks = plan.cs_chunks;
     for (int k = 0; k < 8; ++k) P.base_off[k] = plan.base_off[k];
-    P.Lp = L | 1, P.Lg = (L + 15) / 16 * 16, P.Lv = 16 * plan.k.maxm, P.Pp = (np * (cfg.dv + 1)) | 1, P.Hp = Tr::pitch_H(cfg.k_max);
+    P.Lp = L | 1, P.Lg = (L + 15) / 16 * 16, P.Lv = plan.k.nwt == 1 ? StageOwn::LV : 16 * plan.k.maxm, P.Pp = (np * (cfg.dv + 1)) | 1, P.Hp = Tr::pitch_H(cfg.k_max);
     P.h = T(cfg.h), P.dt = T(cfg.dt), P.tol = T(cfg.tol);
     P.wave_dbg = ((cfg.flags & CGMRES_HIP_FLAG_WAVE_FRESH_TRIG) ? 1 : 0) | ((cfg.flags & CGMRES_HIP_FLAG_WAVE_SERIAL_SWEEPS) ? 2 : 0);
     P.inv_h = T(1.0) / P.h;
@@ -194,6 +199,7 @@ struct CtxWg final : cgmres_hip_ctx {
       t = t + P.dt;                          // cgmres.hpp:107
     }
     P.dtau_h = P.dtau_tab[0], P.dtau_0 = P.dtau_tab[1];
+    v_by_stage = !plan.k.wave && plan.k.nwt == 1;
     if (plan.k.wave)
       k_tick<<<dim3((cfg.batch + Tr::kWaveWpb - 1) / Tr::kWaveWpb), dim3(64 * Tr::kWaveWpb), plan.lds_bytes_tick, stream>>>(P);
     else
@@ -286,6 +292,10 @@ struct CtxWg final : cgmres_hip_ctx {
       if (int rc = rows_h2d(P.dUdt, P.Lg, dUdt, L)) return rc;
     return 0;
   }
+  int state_rows(void** U, void** dUdt, int32_t* pitch) override {
+    *U = P.U, *dUdt = P.dUdt, *pitch = P.Lg;
+    return 0;
+  }
   int get_status(int32_t* n_ax, int32_t* reason) override {
     HIP_TRY(hipSetDevice(cfg.device));
     if (n_ax) HIP_TRY(hipMemcpyAsync(n_ax, P.n_ax, size_t(cfg.batch) * 4, hipMemcpyDeviceToHost, stream));
@@ -296,7 +306,8 @@ struct CtxWg final : cgmres_hip_ctx {
   int get_krylov(void* V, void* H, void* rho, void* g) override {
     HIP_TRY(hipSetDevice(cfg.device));
     const int k1 = cfg.k_max + 1;
-    if (V) {  // rows are pair-interleaved on the device (WgCtx::load_vec): element r + 16 m sits at (m/2)*32 + 2r + (m&1)
+    if (V) {  // rows are pair-interleaved on the device (WgCtx::load_vec): element r + 16 m sits at (m/2)*32 + 2r + (m&1);
+              // rows written by the row-parallel Newton kernel: element 12 r + i at (i/2)*32 + 2r + (i&1) (StageOwn)
       const size_t rows = size_t(cfg.batch) * k1;
       std::vector<T> tmp(rows * P.Lv);
       HIP_TRY(hipMemcpyAsync(tmp.data(), P.V, tmp.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
@@ -305,7 +316,8 @@ struct CtxWg final : cgmres_hip_ctx {
       for (size_t q = 0; q < rows; ++q)
         for (int e = 0; e < L; ++e) {
           const int rr = e & 15, m = e >> 4;
-          dst[q * L + e] = tmp[q * P.Lv + (m >> 1) * 32 + 2 * rr + (m & 1)];
+          const int pos = v_by_stage ? StageOwn::hbm_pos_of_elem(e) : (m >> 1) * 32 + 2 * rr + (m & 1);
+          dst[q * L + e] = tmp[q * P.Lv + pos];
         }
     }
     if (H)
@@ -330,6 +342,7 @@ struct CtxWg final : cgmres_hip_ctx {
     P.x_in = x ? x_dev : nullptr, P.u_out = nullptr, P.x_next = nullptr;
     P.dtau_h = dtau_of(t + P.h);
     P.dtau_0 = dtau_of(t);
+    if (mode == WG_HOOK_GMRES) v_by_stage = false;
     const int keep = P.fh_hbm;
     P.fh_hbm = plan.fh_hbm_hook, P.lds_bytes = int(plan.lds_bytes_hook);  // the hook kernels use the full / fh_hbm plan
     k_hook<<<grid(), block(), plan.lds_bytes_hook, stream>>>(P);

@@ -33,7 +33,10 @@
 //     Arnoldi loop the three phases above give way to ROW-PARALLEL sweeps — every row of 16 lanes runs its instance's
 //     state recurrence as Newton's method on the whole trajectory (four stages per lane, in-row DPP scans) and the
 //     costate recurrence as three scans down the row, all in registers, with no workgroup barrier in the loop
-//     (row_newton_sweep / row_costate); the serial state sweep remains in the preamble only.
+//     (row_newton_sweep / row_costate); the serial state sweep remains in the preamble only.  This kernel
+//     holds its solver vectors in STAGE OWNERSHIP (stage_own.hip.h: lane r has the 12 elements of its own four stages
+//     instead of r + 16 m), so the sweeps take the direction from and leave the result in the registers of the vector
+//     algebra: no work vector W, no row arrays U / Fh — their storage holds lane-private arrays of the owned stages.
 //     NWT = 2 (a state equation affine in x: the semi-active damper): the same with plain scans — no Newton, no serial
 //     sweep and no stage table anywhere in the tick (row_affine_sweep).
 // Statement order inside each instance follows cgmres.hpp:78-175 / gmres.hpp:28-112; what differs from the
@@ -45,6 +48,7 @@
 #include <type_traits>
 
 #include "wave_scan.hip.h"
+#include "stage_own.hip.h"
 #include "dpp.hip.h"
 #include "models.hip.h"
 #include "tick_lane.hip.h"  // sqrt_t / abs_t / FOut
@@ -67,7 +71,8 @@ struct WgParams {
   int base_off[8];
    // Lp/Pp/Hp: odd LDS row pitches (Hp: the COMPACT Hessenberg, column k = rows 0..k at offset k(k+1)/2; h(k+1,k) of the
    // column in progress lives in WgLds::hsub);
-   // Lg: global row pitch (multiple of 16); Lv = 16*MAXM: pitch of the Krylov rows (pads kept zero, no guards)
+   // Lg: global row pitch (multiple of 16); Lv = 16*MAXM (row-parallel Newton kernel: 16*12, stage_own.hip.h): pitch of
+   // the Krylov rows (pads kept zero, no guards)
   T h, dt, tol, inv_h, one_m_zh, dtau_h, dtau_0;
   // closed loop on the device: up to CGM_FUSE_MAX consecutive ticks per launch, the controller state (U in LDS, dUdt
   // in registers, x in LDS) carried from tick to tick without going through HBM; dtau_tab[2*k], [2*k+1] = the two
@@ -148,8 +153,11 @@ __device__ __forceinline__ void cgm_stamp_flush() {
   }
 }
 #define CGM_STAMP(ctx, id) cgm_stamp(id)
+// the same behind the LDS operations in flight: what the stamp closes is a fetch, whose cost is the round trip and not the issue
+#define CGM_STAMP_LDS(ctx, id) (__extension__({ asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); cgm_stamp(id); }))
 #else
 #define CGM_STAMP(ctx, id) ((void)0)
+#define CGM_STAMP_LDS(ctx, id) ((void)0)
 #endif
 
 // ---- LDS carve-up -------------------------------------------------------------------------------
@@ -425,11 +433,15 @@ struct WgCtx {
   struct alignas(2 * sizeof(T)) Pair {
     T a, b;
   };
-  static_assert(MAXM % 2 == 0, "pair-interleaved Krylov rows");
+  // Row-parallel Newton kernel: a lane's NVEC = 12 elements are those of its own four stages (stage_own.hip.h) — the same
+  // row format, slot pair i/2 of lane r at (i/2)*32 + 2r + (i&1) (StageOwn::hbm_pos), rows of 16*NVEC scalars.
+  static constexpr int NVEC = NWT == 1 ? StageOwn::NV : MAXM;  // elements of a solver vector per lane
+  static_assert(NVEC % 2 == 0, "pair-interleaved Krylov rows");
+  __device__ __forceinline__ int vec_elem(int m) const { return NWT == 1 ? StageOwn::elem(r, m) : elem(m); }
   __device__ __forceinline__ void load_vec(T* reg, const T* row) const {
     const Pair* q = reinterpret_cast<const Pair*>(row) + r;
 #pragma unroll
-    for (int m = 0; m < MAXM; m += 2) {
+    for (int m = 0; m < NVEC; m += 2) {
       const Pair t = q[(m / 2) * 16];
       reg[m] = t.a, reg[m + 1] = t.b;
     }
@@ -437,7 +449,7 @@ struct WgCtx {
   __device__ __forceinline__ void store_vec(T* row, const T* reg) const {
     Pair* q = reinterpret_cast<Pair*>(row) + r;
 #pragma unroll
-    for (int m = 0; m < MAXM; m += 2) q[(m / 2) * 16] = Pair{reg[m], reg[m + 1]};
+    for (int m = 0; m < NVEC; m += 2) q[(m / 2) * 16] = Pair{reg[m], reg[m + 1]};
   }
 
   // element q of this row's parameter horizon: LDS row, or (lean) the workgroup's transposed copy in HBM/L2, which the
@@ -467,8 +479,11 @@ struct WgCtx {
   __device__ __forceinline__ void load_common(const T* Ug) {
     constexpr int PMAX = 8;  // ptau entries per lane held in flight (covers dim_p*(dv+1) <= 128)
     const int np_all = M::NP * (P.dv + 1);
-    T urow[MAXM], preg[PMAX], xreg = T(0);
-    if constexpr (!LEAN || U_IN_REGS) load_row_to_reg(urow, Ug, P.Lg);
+    T urow[NVEC], preg[PMAX], xreg = T(0);
+    if constexpr (ROW_NEWTON)
+      so_load_row(urow, Ug);
+    else if constexpr (!LEAN || U_IN_REGS)
+      load_row_to_reg(urow, Ug, P.Lg);
     if (valid) {
 #pragma unroll
       for (int n = 0; n < PMAX; ++n) {
@@ -482,7 +497,10 @@ struct WgCtx {
       for (int m = 0; m < MAXM; ++m) ureg[m] = urow[m];
     }
     if (valid) {
-      if constexpr (!LEAN) reg_to_lds(S.U, urow);
+      if constexpr (ROW_NEWTON)
+        so_put_U(urow);
+      else if constexpr (!LEAN)
+        reg_to_lds(S.U, urow);
 #pragma unroll
       for (int n = 0; n < PMAX; ++n) {
         const int q = r + 16 * n;
@@ -571,7 +589,11 @@ struct WgCtx {
       const bool goq = lt < 4 * IPW && blockIdx.x * IPW + qi < P.B && (!only_active || act_q);
       typename M::QuadLane Q;
       Q.init(rho, mc);
-      const T* __restrict__ U = (PERT || LEAN ? S.W : S.U) + qi * P.Lp;  // PERT: W holds U + h*direction (publish_direction)
+      // PERT: W holds U + h*direction (publish_direction).  Row-parallel Newton kernel: the first controls of every stage,
+      // staged by the stage-owning lanes (so_publish_u0), one word per stage
+      constexpr int US = ROW_NEWTON ? 1 : NU;
+      const T* __restrict__ U = ROW_NEWTON ? so_stage(PERT ? 1 : 0) + qi * StageOwn::stage_pitch(P.dv)
+                                           : (PERT || LEAN ? S.W : S.U) + qi * P.Lp;
       const T dtau1 = Q.sg * dtau;
       T x[NX], v = T(0), amax = T(0);
       if (goq) {
@@ -621,27 +643,27 @@ struct WgCtx {
         int k = 0;
         if constexpr (MODE == 0) {  // rotation mode: four stages per trip (a taken branch costs ~30 cycles)
           for (; k + 4 <= n; k += 4) {
-            const T ub = pu[NU];
+            const T ub = pu[US];
             stage(0, ua);
-            const T uc = pu[2 * NU];
+            const T uc = pu[2 * US];
             stage(1, ub);
-            const T ud = pu[3 * NU];
+            const T ud = pu[3 * US];
             stage(2, uc);
-            ua = pu[4 * NU];
+            ua = pu[4 * US];
             stage(3, ud);
-            pa += 4 * STEP, pv += 4 * STEP, pu += 4 * NU;
+            pa += 4 * STEP, pv += 4 * STEP, pu += 4 * US;
           }
         }
         for (; k + 2 <= n; k += 2) {
-          const T ub = pu[NU];
+          const T ub = pu[US];
           stage(0, ua);
-          ua = pu[2 * NU];
+          ua = pu[2 * US];
           stage(1, ub);
-          pa += 2 * STEP, pv += 2 * STEP, pu += 2 * NU;
+          pa += 2 * STEP, pv += 2 * STEP, pu += 2 * US;
         }
         if (k < n) {  // odd tail: only the last chunk can have one (chunk_len() is even)
           stage(0, ua);
-          pa += STEP, pv += STEP, pu += NU;
+          pa += STEP, pv += STEP, pu += US;
         }
       };
       for (int s0 = 0; s0 < dv; s0 += CH) {
@@ -655,7 +677,7 @@ struct WgCtx {
 #pragma unroll
           for (int c = 0; c < NX; ++c) x[c] = xs[c];
           pa = tab + qi + s0 * STEP, pv = pa + Q.slot_v * IPW;
-          pu = U + s0 * NU;
+          pu = U + s0 * US;
           if (goq) ua = pu[0];
         };
         // v (and with it the rotation) is carried from the previous chunk / quad_begin; only a redo starts from a fresh
@@ -1373,7 +1395,7 @@ struct WgCtx {
 #pragma unroll
     for (int c = 0; c < NX; ++c) x[c] = S.xs[c * IPW + i];
 #pragma unroll
-    for (int j = 0; j < M::NU; ++j) u0[j] = (LEAN ? S.W : S.U)[i * P.Lp + j];  // (lean: call after publish_U)
+    for (int j = 0; j < M::NU; ++j) u0[j] = ROW_NEWTON ? so_unow()[j * IPW + i] : (LEAN ? S.W : S.U)[i * P.Lp + j];  // (lean: call after publish_U)
     model_dxdt(f, x, u0, tr, i, 0);
 #pragma unroll
     for (int c = 0; c < NX; ++c) S.xh[c * IPW + i] = f[c] * P.h + x[c];
@@ -1535,7 +1557,7 @@ struct WgCtx {
   static constexpr int NBASE = 7;  // arrays of RowBase
   struct NoBase {};
   std::conditional_t<ROW_NEWTON, RowBase, NoBase> nb;
-  mutable bool row_moved = true;  // the published direction changed at least one control of this row (publish_direction)
+  mutable bool row_moved = true;  // the direction changed at least one control of this row (row_newton_sweep; NWT = 2: publish_direction)
   // During the Arnoldi loop the base lives in LDS — in the stage table, which only the preamble's state sweeps use, in
   // the scratch of the serial-sweep kernel's costate scan, which this kernel does not use at all, and behind everything
   // else where those two are too small (plan_wg places the arrays: WgParams::base_off) — as pairs [q / 2][thread] per
@@ -1564,6 +1586,86 @@ struct WgCtx {
     }
   }
   T inv_dtau_nb = T(0);
+  // ---- stage ownership (stage_own.hip.h): this kernel's solver vectors are held by the lanes that own their stages, so
+  // the sweeps take the direction from, and leave the result in, the registers of the vector algebra.  What the sweeps
+  // need besides — U and F(U,x+hf,t+h) of the owned stages — sits in two lane-private LDS arrays in the format of the base
+  // arrays: slot pair p of (instance, lane) at pair index (p*IPW + instance)*lanes + lane, lanes = the ceil(dv/4) lanes
+  // that own a stage; 16 bytes per access, the lanes of a workgroup contiguous, every lane reads back what it wrote itself
+  // (no barrier).  Lanes without a stage read the last owning lane's words (finite, masked by their zero step sizes)
+  // and store nothing.  The arrays live in the storage of the row arrays U / Fh / W, which this kernel does not use;
+  // behind them the first controls of U and of U + h dUdt by stage for the preamble's serial sweeps, and the controls of
+  // stage 0 per instance [j*IPW + i] for x + h f and the plant step (StageOwn::lds_scalars).
+  static constexpr int NV = StageOwn::NV;
+  static_assert(!ROW_NEWTON || (SPL == StageOwn::SPL && M::NU == StageOwn::NU && IPW == 16), "stage_own.hip.h");
+  __device__ __forceinline__ int so_lanes() const { return StageOwn::lanes(P.dv); }
+  __device__ __forceinline__ Pair* so_pairs(int which, int thread) const {
+    const int n = so_lanes(), rr = thread & 15, ii = thread >> 4;
+    return reinterpret_cast<Pair*>(S.lds0) + which * (NV / 2) * IPW * n + ii * n + (rr < n ? rr : n - 1);
+  }
+  __device__ __forceinline__ void so_load(int which, T* dst, int thread) const {
+    const Pair* d = so_pairs(which, thread);
+    const int step = IPW * so_lanes();
+#pragma unroll
+    for (int i = 0; i < NV; i += 2) {
+      const Pair t = d[(i / 2) * step];
+      dst[i] = t.a, dst[i + 1] = t.b;
+    }
+  }
+  __device__ __forceinline__ void so_store(int which, const T* src, int thread) const {
+    if ((thread & 15) >= so_lanes()) return;
+    Pair* d = so_pairs(which, thread);
+    const int step = IPW * so_lanes();
+#pragma unroll
+    for (int i = 0; i < NV; i += 2) d[(i / 2) * step] = Pair{src[i], src[i + 1]};
+  }
+  __device__ __forceinline__ T* so_stage(int which) const {  // 0: first controls of U, 1: of U + h dUdt; [instance][stage]
+    return reinterpret_cast<T*>(S.lds0) + 2 * NV * IPW * so_lanes() + which * IPW * StageOwn::stage_pitch(P.dv);
+  }
+  __device__ __forceinline__ T* so_unow() const { return so_stage(2); }
+  // the row's new U: private array + the controls of stage 0
+  __device__ __forceinline__ void so_put_U(const T* u) const {
+    so_store(0, u, tid);
+    if (r == 0) {
+#pragma unroll
+      for (int j = 0; j < M::NU; ++j) so_unow()[j * IPW + inst] = u[j];
+    }
+  }
+  // HBM rows [B][Lg] in the ABI's natural order: a lane moves its 12 contiguous elements, every one behind its e < L guard
+  // (the last owning lane reaches beyond L, at dv = 53 beyond the row's pitch: the next instance's row, or the end of
+  // the allocation).  Once per launch.
+  __device__ __forceinline__ void so_load_row(T* reg, const T* g) const {
+    const T* src = g + size_t(b) * P.Lg;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int e = StageOwn::elem(r, i);
+      reg[i] = (valid && e < P.L) ? src[e] : T(0);
+    }
+  }
+  __device__ __forceinline__ void so_store_row(T* g, const T* reg) const {
+    if (!valid) return;
+    T* dst = g + size_t(b) * P.Lg;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int e = StageOwn::elem(r, i);
+      if (e < P.L) dst[e] = reg[i];
+    }
+  }
+  // the first controls of every owned stage, of U and of U + h d, for the serial sweeps of the preamble (sweep_state);
+  // call in front of the barrier the sweeps start behind
+  __device__ __forceinline__ void so_publish_u0(const T* d) const {
+    if (!valid) return;
+    T us[NV];
+    so_load(0, us, tid);
+    T* row = so_stage(0) + inst * StageOwn::stage_pitch(P.dv) + SPL * r;
+    const int step = IPW * StageOwn::stage_pitch(P.dv);
+#pragma unroll
+    for (int q = 0; q < SPL; ++q) {
+      if (SPL * r + q < P.dv) {
+        row[q] = us[M::NU * q];
+        row[step + q] = d[M::NU * q] * P.h + us[M::NU * q];
+      }
+    }
+  }
   // sin / cos of (base angle + dl) from the base pair, |dl| <= sqrt(rot_zmax)
   __device__ __forceinline__ void rotate(T sb, T cb, T dl, T* sn_out, T* cs_out) const {
     constexpr int NRS = decltype(mc)::NRS, NRC = decltype(mc)::NRC;
@@ -1584,14 +1686,14 @@ struct WgCtx {
   // PendulumDev::costate_step is affine in the costate with (l1, l3) closed in themselves, l0 a running sum over l3 and
   // l2 a geometric recurrence over l0 / l3 — three scans DOWN the row (partner = the lane above), each as local fold,
   // in-row scan, local expansion.  The terminal costate (cgmres.hpp:143) is the starting value of the lane that holds
-  // stage dv (nothing above it but identities).  urow: the row of controls the stages were run with (U, or W = U + h d;
-  // may be `out`'s row: every control is read before the first result is stored).
+  // stage dv (nothing above it but identities).  u: the controls the owned stages were run with (U, or U + h d), out: the
+  // result, both in the stage ownership of the vector algebra (slot 3 q + j = control j of the lane's stage q); stages
+  // beyond the horizon deliver exact zeros, the pads of every solver vector.
   template <int MODE>
   __device__ __forceinline__ void row_costate(const T* x0f, const T* y1, const T* x2f, const T* y3, const T* sd, const T* cd,
-                                              const T* c1, const T* urow, T dtau, T* out, bool run, int tid_o,
-                                              const T* u0_have = nullptr) {  // u0_have: the stages' first controls, if the caller holds them
+                                              const T* c1, const T* u, T dtau, T* out, int tid_o) {
     constexpr int NU = M::NU, NP = M::NP, NBW = M::NBW;
-    static_assert(NU == 3 && NP == 2 && M::NUL == 1, "written for the pendulum's stage");
+    static_assert(NU == 3 && NP == 2 && M::NUL == 1 && NV == SPL * NU, "written for the pendulum's stage");
     const int r = tid_o & 15, inst = tid_o >> 4;
     const int dv = P.dv, s_0 = SPL * r;
     const T ee = -dtau * M::C22, a = T(1) - dtau * M::As;
@@ -1608,34 +1710,39 @@ struct WgCtx {
     const bool has_term = q_term >= 0 && q_term < SPL;
     T bw[SPL][NBW], phi0[SPL];
     T lT[M::NX] = {T(0), T(0), T(0), T(0)};
+    CGM_STAMP(*this, 24);
     {
-      T u0[SPL], u1[SPL], u2[SPL], pp[SPL][NP], fh[SPL][NU];
+      T pp[SPL][NP], fh[NV];
+      // every LDS operand first (parameter addresses clamped into the horizon: no branch, one wait): F(U,x+hf,t+h) of the
+      // owned stages from the lane's private array, the parameters from the instance's row
+      if constexpr (MODE != F_PLAIN) {
+        so_load(1, fh, tid_o);
+      } else {
 #pragma unroll
-      for (int q = 0; q < SPL; ++q) {  // every LDS operand first (addresses clamped into the horizon: no branch, one wait)
-        const int s = s_0 + q, sk = s < dv ? s : dv - 1, sp = s < dv ? s : dv;
-        u0[q] = u0_have ? u0_have[q] : urow[sk * NU];
-        u1[q] = urow[sk * NU + 1], u2[q] = urow[sk * NU + 2];
-#pragma unroll
-        for (int j = 0; j < NP; ++j) pp[q][j] = get_p(inst, sp * NP + j);
-#pragma unroll
-        for (int j = 0; j < NU; ++j) fh[q][j] = MODE == F_PLAIN ? T(0) : S.Fh[inst * P.Lp + sk * NU + j];
+        for (int i = 0; i < NV; ++i) fh[i] = T(0);
       }
 #pragma unroll
       for (int q = 0; q < SPL; ++q) {
-        const int s = s_0 + q;
+        const int s = s_0 + q, sp = s < dv ? s : dv;
+#pragma unroll
+        for (int j = 0; j < NP; ++j) pp[q][j] = get_p(inst, sp * NP + j);
+      }
+      CGM_STAMP_LDS(*this, 27);
+#pragma unroll
+      for (int q = 0; q < SPL; ++q) {
         const T x[M::NX] = {x0f[q], y1[q], x2f[q], y3[q]};
-        const T tg[3] = {sd[q], cd[q], c1[q]}, u[NU] = {u0[q], u1[q], u2[q]};
+        const T tg[3] = {sd[q], cd[q], c1[q]};
+        const T* uq = u + NU * q;
         T phi[NU], bq[NBW];
         // (with the stage's own step size: every coefficient that enters the recurrences carries it as a factor and is
         // zero beyond the horizon; bw[3], which does not, is only used where the stage exists)
-        M::stage_coeffs(bq, phi, x, u, pp[q], tg, dq[q]);
+        M::stage_coeffs(bq, phi, x, uq, pp[q], tg, dq[q]);
 #pragma unroll
         for (int cc = 0; cc < NBW; ++cc) bw[q][cc] = bq[cc];
-        phi0[q] = MODE == F_PLAIN ? phi[0] : (phi[0] * sc_phi - fh[q][0]) * P.inv_h;
-        if (run && tr[q]) {
-          out[inst * P.Lp + s * NU + 1] = MODE == F_PLAIN ? phi[1] : (phi[1] * sc_phi - fh[q][1]) * P.inv_h;
-          out[inst * P.Lp + s * NU + 2] = MODE == F_PLAIN ? phi[2] : (phi[2] * sc_phi - fh[q][2]) * P.inv_h;
-        }
+        phi0[q] = MODE == F_PLAIN ? phi[0] : (phi[0] * sc_phi - fh[NU * q]) * P.inv_h;
+        const T o1 = MODE == F_PLAIN ? phi[1] : (phi[1] * sc_phi - fh[NU * q + 1]) * P.inv_h;
+        const T o2 = MODE == F_PLAIN ? phi[2] : (phi[2] * sc_phi - fh[NU * q + 2]) * P.inv_h;
+        out[NU * q + 1] = tr[q] ? o1 : T(0), out[NU * q + 2] = tr[q] ? o2 : T(0);
         if (q == q_term) M::dPhidx(lT, x, pp[q]);
       }
     }
@@ -1701,14 +1808,10 @@ struct WgCtx {
         l2 = fma_t(fma_t(-M::As, dq[q], T(1)), l2, fma_t(bw[q][2], L3[q], dq[q] * L0[q]));
       }
     }
-    if (run) {
 #pragma unroll
-      for (int q = 0; q < SPL; ++q) {
-        if (tr[q]) {
-          const T dF = fma_t(bw[q][3], L3[q], L2[q] * M::Bs);  // B^T lambda, costate_step
-          out[inst * P.Lp + (s_0 + q) * NU] = fma_t(dF, sc, phi0[q]);
-        }
-      }
+    for (int q = 0; q < SPL; ++q) {
+      const T dF = fma_t(bw[q][3], L3[q], L2[q] * M::Bs);  // B^T lambda, costate_step
+      out[NU * q] = tr[q] ? fma_t(dF, sc, phi0[q]) : T(0);
     }
     CGM_STAMP(*this, 23);
   }
@@ -1843,10 +1946,12 @@ struct WgCtx {
   // The preamble of a tick (see preamble()) for the row-parallel kernel: the three state sweeps stay the serial quad
   // sweeps, side by side on waves 0-2 (#1 leaves its stage table in LDS, #2 / #3 park theirs in HBM); everything behind
   // them — stage coefficients, costate recurrence, dH/du — every row does for itself in registers (row_costate), one
-  // sweep after the other with no workgroup barrier in between: F(U,x+hf,t+h) -> S.Fh, A*dUdt and b through the row
-  // of W into registers.  The stage states of sweep #1, with freshly evaluated sin / cos, become the base of the
+  // sweep after the other with no workgroup barrier in between: F(U,x+hf,t+h) -> the lanes' private array, A*dUdt and b
+  // straight into the registers of the vector algebra.  The stage states of sweep #1, with freshly evaluated sin / cos, become the base of the
   // Newton sweeps (nb; moved to LDS by store_base once every lane is done with the stage table).
-  __device__ __forceinline__ void preamble_rows(T* bb, T* ax0) {
+  // du: dUdt, the direction of the first mat-vec (warm start, cgmres.hpp:99).  Neither b nor A*dUdt passes through LDS.
+  __device__ __forceinline__ void preamble_rows(T* bb, T* ax0, const T* du) {
+    so_publish_u0(du);
     make_xh();
     __syncthreads();
     const size_t tab_n = Lds::tab_count(P.dv);
@@ -1881,7 +1986,8 @@ struct WgCtx {
         if (s > dv) g.x0[q] = T(0), g.x1[q] = T(0), g.x2[q] = T(0);
       }
     };
-    const T* Urow = S.U + inst * P.Lp;
+    T us[NV];  // U of the owned stages
+    so_load(0, us, tid_o);
     {
       Stages g;
       read_stages(g, S.R, xT0);
@@ -1890,31 +1996,39 @@ struct WgCtx {
         nb.x0[q] = g.x0[q], nb.x1[q] = g.x1[q], nb.x2[q] = g.x2[q];
         mc.sincos_pair(g.x0[q] - g.x1[q], g.x1[q], &nb.sd[q], &nb.cd[q], &nb.s1[q], &nb.c1[q]);
       }
-      row_costate<F_PLAIN>(g.x0, g.x1, g.x2, g.x3, g.sd, g.cd, g.c1, Urow, dtau_h, S.Fh, valid, tid_o);
+      T fh[NV];
+      row_costate<F_PLAIN>(g.x0, g.x1, g.x2, g.x3, g.sd, g.cd, g.c1, us, dtau_h, fh, tid_o);
+      so_store(1, fh, tid_o);  // (read back by this same lane only)
     }
     {
       Stages g;
       read_stages(g, tab1, xT2);
-      row_costate<F_AX>(g.x0, g.x1, g.x2, g.x3, g.sd, g.cd, g.c1, S.W + inst * P.Lp, dtau_h, S.W, valid, tid_o);
-      lds_to_reg(ax0, S.W);
+      T uw[NV];  // the controls sweep #3 ran with (the same expression as so_publish_u0)
+#pragma unroll
+      for (int i = 0; i < NV; ++i) uw[i] = du[i] * P.h + us[i];
+      row_costate<F_AX>(g.x0, g.x1, g.x2, g.x3, g.sd, g.cd, g.c1, uw, dtau_h, ax0, tid_o);
     }
     {
       Stages g;
       read_stages(g, tab0, xT1);
-      row_costate<F_RHS>(g.x0, g.x1, g.x2, g.x3, g.sd, g.cd, g.c1, Urow, dtau_0, S.W, valid, tid_o);
-      lds_to_reg(bb, S.W);
+      row_costate<F_RHS>(g.x0, g.x1, g.x2, g.x3, g.sd, g.cd, g.c1, us, dtau_0, bb, tid_o);
     }
     __syncthreads();  // every lane is done with the stage table: the base may move in (store_base)
   }
 
-  // F(U + h d, x + h f, t + h) - F(U, x + h f, t + h), / h, for the row's instance (W holds U + h d on entry, the
-  // result on exit): state recurrence, costate recurrence and dH/du all in the registers of the row's 16 lanes — no
-  // stage table, no workgroup barrier; the only LDS traffic is the row's own operands (W, U, F(U,x+hf,t+h), ptau).
+  // F(U + h d, x + h f, t + h) - F(U, x + h f, t + h), / h, for the row's instance: state recurrence, costate recurrence
+  // and dH/du all in the registers of the row's 16 lanes — no stage table, no workgroup barrier; the only LDS traffic is
+  // reads of the lanes' own operands (U and F(U,x+hf,t+h) of the owned stages, the base trajectory, ptau).
   // COLLECTIVE over the wave (wave-uniform branches on __any).
   // Stages outside the horizon (s >= dv; the last lanes of the row) are IDENTITY maps by construction — their step
   // sizes and coefficients are zeroed once per sweep — so the folds and expansions below carry no per-stage selects.
+  // v: the direction d, out: the result, both in the stage ownership of the vector algebra (NV elements per lane).  Also
+  // sets row_moved: did the direction change any control of this row?  One that the rounding of U + h*d absorbs completely
+  // leaves F unchanged bit for bit in the serial sweeps — A*d = 0 exactly, the reference's breakdown case
+  // (gmres.hpp:63-65) — while Newton's fixed point agrees with the serial trajectory up to rounding only: gmres()
+  // answers that case from this flag.
   template <int MODE, class Mid>
-  __device__ __forceinline__ void row_newton_sweep(T dtau, T* out, bool run, Mid&& mid) {
+  __device__ __forceinline__ void row_newton_sweep(T dtau, const T* v, T* out, bool run, Mid&& mid) {
     constexpr int NU = M::NU;
     static_assert(MODE == F_AX, "only the mat-vec of the Arnoldi loop");
     // (everything below derives from the thread index and is invariant over sweeps and ticks: left visible, the compiler
@@ -1922,22 +2036,32 @@ struct WgCtx {
     // reloaded behind s_waitcnt vmcnt(0), i.e. behind the basis rows in flight)
     int tid_o = tid;
     asm volatile("" : "+v"(tid_o));
-    const int r = tid_o & 15, inst = tid_o >> 4;
+    const int r = tid_o & 15;
     const int dv = P.dv, s_0 = SPL * r;
-    const T* Wr = S.W + inst * P.Lp;
-    const T* Ur = S.U + inst * P.Lp;
     const T ee = -dtau * M::C22;
     bool tr[SPL];            // stage s_0 + q has a transition (s < dv)
     T dq[SPL], eq[SPL];      // its step sizes: dtau, -dtau C22, or 0
-    T u0[SPL], du[SPL];
+    T u[NV], u0[SPL], du[SPL];
+    so_load(0, u, tid_o);  // U of the owned stages
+    {
+      bool moved = false;
 #pragma unroll
-    for (int q = 0; q < SPL; ++q) {
-      tr[q] = s_0 + q < dv;
-      dq[q] = tr[q] ? dtau : T(0), eq[q] = tr[q] ? ee : T(0);
-      const int e = tr[q] ? (s_0 + q) * NU : 0;
-      u0[q] = Wr[e];
-      du[q] = tr[q] ? u0[q] - Ur[e] : T(0);
+      for (int q = 0; q < SPL; ++q) {
+        tr[q] = s_0 + q < dv;
+        dq[q] = tr[q] ? dtau : T(0), eq[q] = tr[q] ? ee : T(0);
+        const T ub = u[NU * q];
+#pragma unroll
+        for (int j = 0; j < NU; ++j) {  // U + h d (cgmres.hpp:166-168); the pads of d and of U are zeros
+          const T uv = v[NU * q + j] * P.h + u[NU * q + j];
+          moved = moved || uv != u[NU * q + j];
+          u[NU * q + j] = uv;
+        }
+        u0[q] = u[NU * q];
+        du[q] = tr[q] ? u0[q] - ub : T(0);
+      }
+      row_moved = ((__ballot(moved) >> (16 * ((tid_o >> 4) & 3))) & 0xffffull) != 0;
     }
+    CGM_STAMP_LDS(*this, 26);
     // (the base trajectory is requested with the controls: one LDS round trip for both)
     T b0[SPL], b2[SPL], y1[SPL], sd[SPL], cd[SPL], s1[SPL], c1[SPL];
     load_base(0, b0, tid_o), load_base(2, b2, tid_o), load_base(1, y1, tid_o);
@@ -2065,7 +2189,7 @@ struct WgCtx {
       }
     }
     mid();
-    row_costate<MODE>(x0f, y1, x2f, y3, sd, cd, c1, Wr, dtau, out, run, tid_o, u0);
+    row_costate<MODE>(x0f, y1, x2f, y3, sd, cd, c1, u, dtau, out, tid_o);
   }
 
   // Hessenberg column k of one instance: stored reflectors, new reflector, residual rotation (gmres.hpp:71-90) — scalar
@@ -2108,7 +2232,7 @@ struct WgCtx {
     auto hoff = [](int k) { return (k * (k + 1)) >> 1; };
     T* rhoi = S.rho + inst * k1;
     T* gi = S.g + inst * 3 * kmax;
-    T vcur[MAXM], w[MAXM];
+    T vcur[NVEC], w[NVEC];
     // Ring of NBUF register buffers for the older basis vectors: NBUF rows are requested before the sweep starts, and
     // every buffer is refilled with row i+NBUF as soon as round i has consumed it, so each load has NBUF-1 rounds
     // (~1000 cycles) to arrive.  Static buffer indices: one fully unrolled instance per iteration count (<= KRING).
@@ -2139,7 +2263,7 @@ struct WgCtx {
     // rows from NKEEP on.  Pays for itself only where registers are left: the one-workgroup-per-CU kernels with short
     // vectors, with the solution vector parked in HBM for the duration of the loop like the long-vector kernels do.
     constexpr int NKEEP = (!LEAN && MAXM <= 10) ? 2 : 0;
-    T vkeep[NKEEP > 0 ? NKEEP : 1][MAXM];
+    T vkeep[NKEEP > 0 ? NKEEP : 1][NVEC];
     // workgroup-uniform; longer bases use the plain streaming loop.  So does the lean plan: with 256 registers per wave the
     // twelve straight-line copies of the rounds push everything that lives across them (U, the sweep constants) into
     // scratch — in every block of the kernel, executed or not.
@@ -2155,7 +2279,7 @@ struct WgCtx {
     {
       T ss = 0;
 #pragma unroll
-      for (int m = 0; m < MAXM; ++m) {
+      for (int m = 0; m < NVEC; ++m) {
         vcur[m] = bb[m] - ax0[m];
         ss += vcur[m] * vcur[m];
       }
@@ -2172,13 +2296,13 @@ struct WgCtx {
       if (active) {
         const T inv = T(1.0) / rho0;  // gmres.hpp:44
 #pragma unroll
-        for (int m = 0; m < MAXM; ++m) vcur[m] = vcur[m] * inv;
+        for (int m = 0; m < NVEC; ++m) vcur[m] = vcur[m] * inv;
         store_vec(vrow(0), vcur);
         if constexpr (NKEEP > 0) {
 #pragma unroll
-          for (int m = 0; m < MAXM; ++m) vkeep[0][m] = vcur[m];
+          for (int m = 0; m < NVEC; ++m) vkeep[0][m] = vcur[m];
         }
-        publish_direction(vcur);
+        if constexpr (!ROW_NEWTON) publish_direction(vcur);  // (stage ownership: v_k is where the sweep needs it)
       }
       if (r == 0) S.flag[inst] = active ? 1 : 0;
     }
@@ -2237,7 +2361,7 @@ struct WgCtx {
       // The first basis vectors this iteration needs are requested from HBM/L2 early.  Waves 1-3 do it NOW (the rows
       // arrive while wave 0 sweeps); wave 0 — four waves' row requests take the CU's address unit ~800 cycles, which
       // would delay the sweep — does it after its state sweep, where it otherwise waits for the coefficient tail.
-      T vbuf[NBUF][MAXM];
+      T vbuf[NBUF][NVEC];
       // (vmcnt(0) first: the two call sites below write the same registers, so without it the compiler must assume the
       // other site's requests are still in flight — with an in-order counter and conditional requests that leaves it
       // only s_waitcnt vmcnt(0) in front of EVERY row: each request waited for the previous row to arrive, on wave 0
@@ -2268,18 +2392,21 @@ struct WgCtx {
           request_rows();  // (a light sweep: the rows may be in flight across it)
           row_affine_sweep<F_AX>(S.xh, dtau_h, S.W + inst * P.Lp, S.W, active);
         } else {
-          row_newton_sweep<F_AX>(dtau_h, S.W, active, request_rows);  // :48  W <- A v_k, in place
+          row_newton_sweep<F_AX>(dtau_h, vcur, w, active, request_rows);  // :48  w <- A v_k, registers to registers
         }
         CGM_STAMP(*this, 6);
       } else {
         ax(true, request_rows, deferred_column);  // :48  W <- A v_k, in place
       }
       if (active) {
-        lds_to_reg(w, S.W);
+        if constexpr (!ROW_NEWTON) {
+          lds_to_reg(w, S.W);
+          if constexpr (NWT != 0) CGM_STAMP_LDS(*this, 2);
+        }
         if constexpr (NWT != 0) {
           if (!row_moved) {  // (see publish_direction)
 #pragma unroll
-            for (int m = 0; m < MAXM; ++m) w[m] = T(0);
+            for (int m = 0; m < NVEC; ++m) w[m] = T(0);
           }
         }
         T* Hk = Hi + hoff(k);
@@ -2287,13 +2414,13 @@ struct WgCtx {
         auto mgs_round = [&](const T* vi, int i) {
           T pa = 0, pb = 0;  // two partial sums: the fp64 FMA chain is latency-bound (8 cycles/op dependent)
 #pragma unroll
-          for (int m = 0; m < MAXM; m += 2) {
+          for (int m = 0; m < NVEC; m += 2) {
             pa += vi[m] * w[m];
-            if (m + 1 < MAXM) pb += vi[m + 1] * w[m + 1];
+            if (m + 1 < NVEC) pb += vi[m + 1] * w[m + 1];
           }
           const T hik = row16_sum(pa + pb);
 #pragma unroll
-          for (int m = 0; m < MAXM; ++m) w[m] = w[m] - vi[m] * hik;
+          for (int m = 0; m < NVEC; ++m) w[m] = w[m] - vi[m] * hik;
           if (r == 0) Hk[i] = hik;
         };
         if (preload) {
@@ -2327,7 +2454,7 @@ struct WgCtx {
           // wait for the newest request): the main loop does SDEPTH rounds per trip and refills each buffer right after
           // its round (row index clamped: the last trips re-read the last row), the remaining < SDEPTH rounds find
           // their rows already requested.
-          T vq[SDEPTH][MAXM];
+          T vq[SDEPTH][NVEC];
           const int kk = VK_IN_REGS ? k : k + 1;
           if (kk > 0) {
 #pragma unroll
@@ -2353,9 +2480,9 @@ struct WgCtx {
         if constexpr (VK_IN_REGS) mgs_round(vcur, k);
         T na = 0, nb = 0;
 #pragma unroll
-        for (int m = 0; m < MAXM; m += 2) {
+        for (int m = 0; m < NVEC; m += 2) {
           na += w[m] * w[m];
-          if (m + 1 < MAXM) nb += w[m + 1] * w[m + 1];
+          if (m + 1 < NVEC) nb += w[m + 1] * w[m + 1];
         }
         CGM_STAMP(*this, 7);
         const T hn = sqrt_t<T>(row16_sum(na + nb));  // :60
@@ -2372,17 +2499,21 @@ struct WgCtx {
         } else {
           const T inv = T(1.0) / hn;  // :67
 #pragma unroll
-          for (int m = 0; m < MAXM; ++m) vcur[m] = w[m] * inv;
+          for (int m = 0; m < NVEC; ++m) vcur[m] = w[m] * inv;
           store_vec(vrow(k + 1), vcur);
           if constexpr (NKEEP > 1) {
 #pragma unroll
             for (int q = 1; q < NKEEP; ++q)
               if (k + 1 == q) {
 #pragma unroll
-                for (int m = 0; m < MAXM; ++m) vkeep[q][m] = vcur[m];
+                for (int m = 0; m < NVEC; ++m) vkeep[q][m] = vcur[m];
               }
           }
-          publish_direction(vcur);
+          if constexpr (!ROW_NEWTON) {
+            if constexpr (NWT != 0) CGM_STAMP(*this, 8);
+            publish_direction(vcur);
+            if constexpr (NWT != 0) CGM_STAMP_LDS(*this, 25);
+          }
           // Hessenberg column k: stored reflectors, new reflector, residual rotation (:71-90) — scalar work.
           // Every lane of the row computes it from the same LDS words (broadcast reads; a row never straddles
           // a wave, and LDS operations of one wave complete in order), lane 0 writes back: the convergence
@@ -2449,7 +2580,7 @@ struct WgCtx {
     const int reason = S.reason[inst];
     const int ks = reason == 0 ? (valid ? kmax : 0) : (reason == 1 ? S.ksolve[inst] : 0);
     // the first basis rows of the x update are requested before the (serial) back substitution
-    T vbx[NBUF][MAXM];
+    T vbx[NBUF][NVEC];
     if (preload && valid && reason <= 1) {
 #pragma unroll
       for (int j = 0; j < NBUF; ++j)
@@ -2503,9 +2634,9 @@ struct WgCtx {
     CGM_STAMP(*this, 11);
     if (valid && reason <= 1) {
       // x += V[:,0:ks] y  (gmres.hpp:110-111), accumulated j-ascending from 0 like matrix.hpp:82-91
-      T acc[MAXM];
+      T acc[NVEC];
 #pragma unroll
-      for (int m = 0; m < MAXM; ++m) acc[m] = T(0.0);
+      for (int m = 0; m < NVEC; ++m) acc[m] = T(0.0);
       if (preload) {  // same register ring as the Gram-Schmidt rounds
         auto& vbuf = vbx;
         auto rounds = [&](auto kc) {
@@ -2516,12 +2647,12 @@ struct WgCtx {
             if constexpr (NKEEP > 0) {
               if (j < NKEEP) {
 #pragma unroll
-                for (int m = 0; m < MAXM; ++m) acc[m] += vkeep[j < NKEEP ? j : 0][m] * yj;
+                for (int m = 0; m < NVEC; ++m) acc[m] += vkeep[j < NKEEP ? j : 0][m] * yj;
                 continue;
               }
             }
 #pragma unroll
-            for (int m = 0; m < MAXM; ++m) acc[m] += vbuf[(j - NKEEP) % NBUF][m] * yj;
+            for (int m = 0; m < NVEC; ++m) acc[m] += vbuf[(j - NKEEP) % NBUF][m] * yj;
             if (j + NBUF < K) load_vec(vbuf[(j - NKEEP) % NBUF], vrow(j + NBUF));
           }
         };
@@ -2531,7 +2662,7 @@ struct WgCtx {
         }
       } else {
         // streaming form, SDEPTH rows in flight (see the Gram-Schmidt loop)
-        T vq[SDEPTH][MAXM];
+        T vq[SDEPTH][NVEC];
         if (ks > 0) {
 #pragma unroll
           for (int d = 0; d < SDEPTH; ++d) load_vec(vq[d], vrow(d < ks ? d : ks - 1));
@@ -2539,7 +2670,7 @@ struct WgCtx {
         auto axpy = [&](const T* vj, int j) {
           const T yj = rhoi[j];
 #pragma unroll
-          for (int m = 0; m < MAXM; ++m) acc[m] += vj[m] * yj;
+          for (int m = 0; m < NVEC; ++m) acc[m] += vj[m] * yj;
         };
         int j = 0;
         for (; j + SDEPTH <= ks; j += SDEPTH) {
@@ -2557,11 +2688,11 @@ struct WgCtx {
         drain_stream();
       }
 #pragma unroll
-      for (int m = 0; m < MAXM; ++m) xv[m] = xv[m] + acc[m];
+      for (int m = 0; m < NVEC; ++m) xv[m] = xv[m] + acc[m];
     }
     if (valid && reason == 4) {  // CGMRES_HIP_EXIT_NONFINITE: what the reference's fall-through ends with
 #pragma unroll
-      for (int m = 0; m < MAXM; ++m) xv[m] = elem(m) < P.L ? quiet_nan<T>() : T(0);
+      for (int m = 0; m < NVEC; ++m) xv[m] = vec_elem(m) < P.L ? quiet_nan<T>() : T(0);
     }
   }
 
@@ -2594,9 +2725,15 @@ __global__ __launch_bounds__(IPW * 16) __attribute__((amdgpu_waves_per_eu(LEAN ?
     WgParams<T> P) {
   extern __shared__ __align__(16) unsigned char smem[];
   WgCtx<M, T, IPW, MAXM, LEAN, PAR, NWT> C(P, smem);
-  T du[MAXM], bb[MAXM];
+  using Ctx = decltype(C);
+  constexpr bool SO = Ctx::ROW_NEWTON;  // solver vectors in stage ownership (stage_own.hip.h)
+  constexpr int NVEC = Ctx::NVEC;
+  T du[NVEC], bb[NVEC];
   C.load_common(P.U);
-  C.load_row_to_reg(du, P.dUdt, P.Lg);
+  if constexpr (SO)
+    C.so_load_row(du, P.dUdt);
+  else
+    C.load_row_to_reg(du, P.dUdt, P.Lg);
   const int nt = P.n_ticks;
   for (int tk = 0; tk < nt; ++tk) {
     const bool last = tk + 1 == nt;
@@ -2606,12 +2743,12 @@ __global__ __launch_bounds__(IPW * 16) __attribute__((amdgpu_waves_per_eu(LEAN ?
     if (M::NP > 0 && P.ptau_seq) C.load_ptau_tick(P.ptau_seq + size_t(tk) * P.pseq_tick);
     __syncthreads();  // (also drains the prologue's / load_ptau_tick's HBM stores of the lean parameter table)
     CGM_STAMP(C, 0);
-    if constexpr (!LEAN) C.publish_direction(du);  // direction of the first mat-vec: x0 = dUdt (warm start, cgmres.hpp:99)
-    T ax0[MAXM];
+    if constexpr (!LEAN && !SO) C.publish_direction(du);  // direction of the first mat-vec: x0 = dUdt (warm start, cgmres.hpp:99)
+    T ax0[NVEC];
     if constexpr (NWT == 2) {
       C.preamble_affine(bb, ax0);
     } else if constexpr (NWT == 1) {
-      C.preamble_rows(bb, ax0);
+      C.preamble_rows(bb, ax0, du);
       C.store_base();
     } else {
       C.template preamble<true>(bb, ax0, du);  // Fh in LDS (or HBM); b and A*dUdt in registers
@@ -2620,23 +2757,42 @@ __global__ __launch_bounds__(IPW * 16) __attribute__((amdgpu_waves_per_eu(LEAN ?
     C.gmres(du, bb, ax0);
     CGM_STAMP(C, 12);
     // U += dUdt*dt, u = U[0:dim_u]  (cgmres.hpp:102-109)
-    T un[MAXM];
-    if constexpr (LEAN) {
+    T un[NVEC];
+    if constexpr (SO) {
+      C.so_load(0, un, C.tid);  // (lanes without a stage hold another lane's words here: never stored)
+    } else if constexpr (LEAN) {
       C.get_urow(un);
     } else {
       C.lds_to_reg(un, C.S.U);
     }
 #pragma unroll
-    for (int m = 0; m < MAXM; ++m) un[m] = un[m] + du[m] * P.dt;
+    for (int m = 0; m < NVEC; ++m) un[m] = un[m] + du[m] * P.dt;
     constexpr bool U_ROW_IS_HBM = LEAN && !decltype(C)::U_IN_REGS;  // then every tick writes its U row
-    if (last || U_ROW_IS_HBM) C.reg_to_row(P.U, P.Lg, un);
+    if constexpr (SO) {
+      if (last) {
+        C.so_store_row(P.U, un);
+        C.so_store_row(P.dUdt, du);
+        if (C.valid && C.r == 0) {  // u = the controls of stage 0: slots 0 .. NU-1 of lane 0
+#pragma unroll
+          for (int j = 0; j < M::NU; ++j) P.u_out[size_t(C.b) * M::NU + j] = un[j];
+        }
+      }
+    } else {
+      if (last || U_ROW_IS_HBM) C.reg_to_row(P.U, P.Lg, un);
+    }
     if (last) {  // the rest of the controller state goes back to HBM with the last tick of the launch only
-      C.reg_to_row(P.dUdt, P.Lg, du);
-      if (C.valid && C.r < M::NU) P.u_out[size_t(C.b) * M::NU + C.r] = un[0];  // element e = r (m = 0), r < NU <= 16
+      if constexpr (!SO) {
+        C.reg_to_row(P.dUdt, P.Lg, du);
+        if (C.valid && C.r < M::NU) P.u_out[size_t(C.b) * M::NU + C.r] = un[0];  // element e = r (m = 0), r < NU <= 16
+      }
       C.store_status();
       // x_dxh and F_dxh_h of this tick stay with the controller like the reference's members (cgmres.hpp:198-201):
       // a white-box Ax_func after control() evaluates with them (with fh_hbm the preamble has stored the row already)
-      if (!C.fh_hbm()) {
+      if constexpr (SO) {
+        T fh[NVEC];
+        C.so_load(1, fh, C.tid);
+        C.so_store_row(P.Fh, fh);
+      } else if (!C.fh_hbm()) {
         T fh[MAXM];
         C.lds_to_reg(fh, C.S.Fh);
         C.reg_to_row(P.Fh, P.Lg, fh);
@@ -2650,6 +2806,8 @@ __global__ __launch_bounds__(IPW * 16) __attribute__((amdgpu_waves_per_eu(LEAN ?
         for (int m = 0; m < MAXM; ++m) C.ureg[m] = un[m];
       }
       if (C.valid && C.r < M::NU) C.S.u0[C.r * IPW + C.inst] = un[0];
+    } else if constexpr (SO) {
+      if (C.valid) C.so_put_U(un);
     } else {
       C.reg_to_lds(C.S.U, un);
     }
@@ -2661,7 +2819,7 @@ __global__ __launch_bounds__(IPW * 16) __attribute__((amdgpu_waves_per_eu(LEAN ?
 #pragma unroll
         for (int c = 0; c < M::NX; ++c) x[c] = C.S.xs[c * IPW + i];
 #pragma unroll
-        for (int j = 0; j < M::NU; ++j) u[j] = LEAN ? C.S.u0[j * IPW + i] : C.S.U[i * P.Lp + j];
+        for (int j = 0; j < M::NU; ++j) u[j] = LEAN ? C.S.u0[j * IPW + i] : (SO ? C.so_unow()[j * IPW + i] : C.S.U[i * P.Lp + j]);
         C.model_dxdt(f, x, u, tr, i, 0);  // the example's plant = the model's own state equation (p of stage 0)
 #pragma unroll
         for (int c = 0; c < M::NX; ++c) {

@@ -194,6 +194,10 @@ int cgmres_hip_synchronize(cgmres_hip_handle h);
 int cgmres_hip_get_time(cgmres_hip_handle h, double* t);
 int cgmres_hip_get_state(cgmres_hip_handle h, double* t, void* U, void* dUdt); /* [batch][dim_u*dv]; NULL skips */
 int cgmres_hip_set_state(cgmres_hip_handle h, double t, const void* U, const void* dUdt);
+/* Device addresses of U and dUdt as the kernels keep them: [batch][*pitch] scalars, *pitch >= dim_u*dv; the words behind
+ * dim_u*dv of a row are pads that no kernel reads or writes and get_state / set_state skip.  Valid while the handle
+ * lives; synchronise before touching them.  Mappings that keep their state in another form return NULL addresses. */
+int cgmres_hip_state_rows(cgmres_hip_handle h, void** U_dev, void** dUdt_dev, int32_t* pitch);
 /* n_ax[b] = Arnoldi mat-vecs executed inside the k loop of the last solve, reason[b] = CGMRES_HIP_EXIT_* */
 int cgmres_hip_get_status(cgmres_hip_handle h, int32_t* n_ax, int32_t* reason);
 /* H [batch][(k_max+1)*(k_max+1)] column-major ld k_max+1 (gmres.hpp:12,54), rho [batch][k_max+1],

@@ -56,6 +56,8 @@ names = {14: "loop top: before barrier_or", 15: "barrier_or (drains V row store)
          16: "costate A: four chunks side by side (record store when 18-20 are stamped)", 17: "costate: barrier",
          6: "sweep phase 3 (costate; B: boundaries + combine if chunk-parallel)", 7: "MGS rounds", 8: "norm+normalise+store",
          21: "row Newton: x0/x2 scans", 22: "row Newton: iterations (visits = iterations)", 23: "row Newton: costate scans + out", 24: "row Newton: operands + stage coefficients",
+         25: "row Newton: publish_direction (U + h v -> W)", 26: "row Newton: control fetch at the sweep head", 27: "row Newton: costate operand fetch",
+         2: "row Newton: result row -> registers",
          9: "Hessenberg scalar", 10: "loop exit barrier", 11: "back-subst", 12: "x update (V*y)", 13: "epilogue"}
 if c.variant == 4:  # the wave mapping's own stamp ids (tick_wave.hip.h)
     names = {11: "tick top / epilogue tail", 0: "x+hf, control rows", 1: "serial state sweeps (3 quads)", 2: "preamble: 3 x costate scans",
