@@ -21,7 +21,7 @@ F64, F32 = 0, 1
 EXIT_NATURAL, EXIT_CONVERGED, EXIT_SMALL_RESIDUAL, EXIT_BREAKDOWN, EXIT_NONFINITE = 0, 1, 2, 3, 4
 FLAG_SERIAL_COSTATE, FLAG_IPW8, FLAG_NO_BINNING, FLAG_TWO_PASS_COSTATE = 1, 2, 4, 8
 FLAG_NO_WAVE, FLAG_WAVE_FRESH_TRIG, FLAG_WAVE_SERIAL_SWEEPS, FLAG_SERIAL_STATE_SWEEP = 16, 32, 64, 128
-ABI_VERSION = 2
+ABI_VERSION = 3
 TICKS_PER_LAUNCH = 10  # CGMRES_HIP_TICKS_PER_LAUNCH: closed_loop_device fuses this many ticks per launch (wg mapping)
 
 # every symbol include/cgmres_hip.h declares (tests/test_capi_symbols.py checks header == this == library)
@@ -32,7 +32,7 @@ SYMBOLS = [
     "cgmres_hip_device_count", "cgmres_hip_create", "cgmres_hip_destroy", "cgmres_hip_get_config", "cgmres_hip_variant_name",
     "cgmres_hip_set_ptau", "cgmres_hip_set_ptau_repeat", "cgmres_hip_init_u0", "cgmres_hip_init_u0_newton",
     "cgmres_hip_control", "cgmres_hip_control_device", "cgmres_hip_closed_loop_device",
-    "cgmres_hip_closed_loop_device_ptau", "cgmres_hip_synchronize", "cgmres_hip_shard_bounds",
+    "cgmres_hip_closed_loop_device_ptau", "cgmres_hip_closed_loop_device_ex", "cgmres_hip_synchronize", "cgmres_hip_shard_bounds",
     "cgmres_hip_get_time", "cgmres_hip_get_state", "cgmres_hip_set_state", "cgmres_hip_get_status",
     "cgmres_hip_get_krylov", "cgmres_hip_F_func", "cgmres_hip_prepare", "cgmres_hip_Ax_func", "cgmres_hip_gmres",
     "cgmres_hip_timer_start", "cgmres_hip_timer_stop", "cgmres_hip_malloc", "cgmres_hip_free",
@@ -46,6 +46,13 @@ class Config(C.Structure):
                 ("dv", C.c_int32), ("k_max", C.c_int32), ("device", C.c_int32), ("variant", C.c_int32),
                 ("flags", C.c_int32), ("reserved", C.c_int32), ("tol", C.c_double), ("dt", C.c_double), ("h", C.c_double), ("zeta", C.c_double),
                 ("Tf", C.c_double), ("alpha", C.c_double), ("stream", C.c_void_p)]
+
+
+class LoopInputs(C.Structure):
+    """struct cgmres_hip_loop_inputs (include/cgmres_hip.h): the per-tick input sequences of closed_loop_device_ex."""
+    _fields_ = [("struct_size", C.c_int32), ("ptau_per_instance", C.c_int32), ("dist_per_instance", C.c_int32),
+                ("meas_per_instance", C.c_int32), ("ptau_seq_dev", C.c_void_p), ("dist_seq_dev", C.c_void_p),
+                ("meas_seq_dev", C.c_void_p)]
 
 
 class CgmresHipError(RuntimeError):
@@ -93,6 +100,7 @@ def load():
     lib.cgmres_hip_control_device.argtypes = [vp, vp, vp]
     lib.cgmres_hip_closed_loop_device.argtypes = [vp, vp, vp, i32]
     lib.cgmres_hip_closed_loop_device_ptau.argtypes = [vp, vp, vp, i32, vp, C.c_int]
+    lib.cgmres_hip_closed_loop_device_ex.argtypes = [vp, vp, vp, i32, C.POINTER(LoopInputs)]
     lib.cgmres_hip_synchronize.argtypes = [vp]
     lib.cgmres_hip_shard_bounds.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.cgmres_hip_get_time.argtypes = [vp, C.POINTER(C.c_double)]
@@ -369,17 +377,34 @@ class CgmresBatch:
         _check(load().cgmres_hip_control_device(self._h, _ptr(u_dev, self.np_dtype, self.batch * self.dim_u),
                                                 _ptr(x_dev, self.np_dtype, self.batch * self.dim_x)))
 
-    def closed_loop_device(self, x_dev, u_dev, n_ticks, ptau_seq_dev=None, per_instance=True):
+    def closed_loop_device(self, x_dev, u_dev, n_ticks, ptau_seq_dev=None, per_instance=True, *, dist_seq_dev=None,
+                           meas_seq_dev=None, dist_per_instance=True, meas_per_instance=True):
         """n_ticks of the example main loop on the device.  ptau_seq_dev: optional device array of per-tick parameter
-        horizons, [n_ticks, batch, dim_p*(dv+1)] (per_instance) or [n_ticks, dim_p*(dv+1)] — `set_ptau` before every tick."""
+        horizons, [n_ticks, batch, dim_p*(dv+1)] (per_instance) or [n_ticks, dim_p*(dv+1)] — `set_ptau` before every tick.
+        dist_seq_dev / meas_seq_dev: optional device arrays [n_ticks, batch, dim_x] (or [n_ticks, dim_x], broadcast) of a
+        process disturbance d and a measurement noise v: y_k = x_k + v_k, u_k = control(y_k),
+        x_{k+1} = (x_k + f(x_k, u_k)*dt) + d_k; x_dev holds the TRUE state (cgmres_hip_closed_loop_device_ex)."""
         xp = _ptr(x_dev, self.np_dtype, self.batch * self.dim_x)
         up = _ptr(u_dev, self.np_dtype, self.batch * self.dim_u)
-        if ptau_seq_dev is None or self.dim_p == 0:
-            _check(load().cgmres_hip_closed_loop_device(self._h, xp, up, int(n_ticks)))
-        else:
-            n = int(n_ticks) * (self.batch if per_instance else 1) * self.dim_p * (self.dv + 1)
-            _check(load().cgmres_hip_closed_loop_device_ptau(self._h, xp, up, int(n_ticks),
-                                                             _ptr(ptau_seq_dev, self.np_dtype, n), 1 if per_instance else 0))
+        if ptau_seq_dev is not None and self.dim_p == 0:
+            ptau_seq_dev = None
+        if dist_seq_dev is None and meas_seq_dev is None:
+            if ptau_seq_dev is None:
+                _check(load().cgmres_hip_closed_loop_device(self._h, xp, up, int(n_ticks)))
+            else:
+                n = int(n_ticks) * (self.batch if per_instance else 1) * self.dim_p * (self.dv + 1)
+                _check(load().cgmres_hip_closed_loop_device_ptau(self._h, xp, up, int(n_ticks),
+                                                                 _ptr(ptau_seq_dev, self.np_dtype, n), 1 if per_instance else 0))
+            return
+        li = LoopInputs(struct_size=C.sizeof(LoopInputs), ptau_per_instance=1 if per_instance else 0,
+                        dist_per_instance=1 if dist_per_instance else 0, meas_per_instance=1 if meas_per_instance else 0)
+
+        def count(per, width):  # (a negative n_ticks is the library's to refuse)
+            return int(n_ticks) * (self.batch if per else 1) * width if int(n_ticks) >= 0 else None
+        li.ptau_seq_dev = _ptr(ptau_seq_dev, self.np_dtype, count(per_instance, self.dim_p * (self.dv + 1)))
+        li.dist_seq_dev = _ptr(dist_seq_dev, self.np_dtype, count(dist_per_instance, self.dim_x))
+        li.meas_seq_dev = _ptr(meas_seq_dev, self.np_dtype, count(meas_per_instance, self.dim_x))
+        _check(load().cgmres_hip_closed_loop_device_ex(self._h, xp, up, int(n_ticks), C.byref(li)))
 
     def synchronize(self):
         _check(load().cgmres_hip_synchronize(self._h))

@@ -394,14 +394,49 @@ int cgmres_hip_control_device(cgmres_hip_handle h, void* u, const void* x) {
 int cgmres_hip_closed_loop_device(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks) {
   NEED(h);
   if (n_ticks < 0) return fail(CGMRES_HIP_EINVAL, "n_ticks < 0");
-  return h->closed_loop(x, u, n_ticks);
+  return h->closed_loop(x, u, n_ticks, cgm::LoopSeqs{});
 }
 int cgmres_hip_closed_loop_device_ptau(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const void* ptau_seq,
                                        int per_instance) {
   NEED(h);
   if (n_ticks < 0) return fail(CGMRES_HIP_EINVAL, "n_ticks < 0");
   if (h->np && !ptau_seq) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ptau: null ptau sequence");
-  return h->closed_loop(x, u, n_ticks, h->np ? ptau_seq : nullptr, per_instance);
+  cgm::LoopSeqs sq;
+  sq.ptau = h->np ? ptau_seq : nullptr, sq.ptau_per_instance = per_instance;
+  return h->closed_loop(x, u, n_ticks, sq);
+}
+int cgmres_hip_closed_loop_device_ex(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const cgmres_hip_loop_inputs* in) {
+  NEED(h);
+  if (n_ticks < 0) return fail(CGMRES_HIP_EINVAL, "n_ticks < 0");
+  cgm::LoopSeqs sq;
+  if (in) {
+    if (in->struct_size != int32_t(sizeof(cgmres_hip_loop_inputs)))
+      return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: struct_size %d, this library's cgmres_hip_loop_inputs has %d",
+                  in->struct_size, int(sizeof(cgmres_hip_loop_inputs)));
+    const int32_t pi[3] = {in->ptau_per_instance, in->dist_per_instance, in->meas_per_instance};
+    for (int32_t v : pi)
+      if (v != 0 && v != 1) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: a *_per_instance field is %d, not 0 or 1", v);
+    // the reference's alias guard (cgmres.hpp:119-124): an input sequence must not share bytes with the loop's outputs
+    const size_t es = h->cfg.dtype == CGMRES_HIP_F32 ? 4 : 8, B = size_t(h->cfg.batch);
+    auto overlaps = [&](const void* seq, int per_instance, const void* out, size_t out_bytes) {
+      if (!seq || !out) return false;
+      const uintptr_t a = reinterpret_cast<uintptr_t>(seq), b = reinterpret_cast<uintptr_t>(out);
+      const size_t seq_bytes = size_t(n_ticks) * (per_instance ? B : 1) * h->nx * es;
+      return a < b + out_bytes && b < a + seq_bytes;
+    };
+    const struct { const char* name; const void* p; int pi; } seqs[2] = {{"dist_seq_dev", in->dist_seq_dev, in->dist_per_instance},
+                                                                        {"meas_seq_dev", in->meas_seq_dev, in->meas_per_instance}};
+    for (const auto& s : seqs) {
+      if (overlaps(s.p, s.pi, x, B * h->nx * es))
+        return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: %s overlaps x_dev (cgmres.hpp DEBUG_MODE alias guard)", s.name);
+      if (overlaps(s.p, s.pi, u, B * h->nu * es))
+        return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: %s overlaps u_dev (cgmres.hpp DEBUG_MODE alias guard)", s.name);
+    }
+    sq.ptau = h->np ? in->ptau_seq_dev : nullptr, sq.ptau_per_instance = in->ptau_per_instance;
+    sq.dist = in->dist_seq_dev, sq.dist_per_instance = in->dist_per_instance;
+    sq.meas = in->meas_seq_dev, sq.meas_per_instance = in->meas_per_instance;
+  }
+  return h->closed_loop(x, u, n_ticks, sq);
 }
 int cgmres_hip_shard_bounds(int32_t n, int32_t world, int32_t rank, int32_t* lo, int32_t* hi) {
   if (n < 0 || world < 1 || rank < 0 || rank >= world || !lo || !hi)

@@ -37,6 +37,19 @@ inline int fail(int code, const char* fmt, ...) {
 
 }  // namespace cgm
 
+namespace cgm {
+// Per-tick input sequences of the closed loop (cgmres_hip_loop_inputs, validated by capi.hip): device pointers,
+// [n_ticks][batch or 1][...]; null = absent
+struct LoopSeqs {
+  const void* ptau = nullptr;  // set_ptau before every tick (cgmres.hpp:36-39)
+  int ptau_per_instance = 0;
+  const void* dist = nullptr;  // d: added to the plant step
+  int dist_per_instance = 0;
+  const void* meas = nullptr;  // v: added to the state the controller is shown
+  int meas_per_instance = 0;
+};
+}  // namespace cgm
+
 // Type-erased controller batch: what a cgmres_hip_handle points to.
 struct cgmres_hip_ctx {
   cgmres_hip_config cfg{};
@@ -101,7 +114,7 @@ struct cgmres_hip_ctx {
   virtual int init_u0_newton(void*, const void*, const void*, int) = 0;
   virtual int control_host(void*, const void*) = 0;
   virtual int control_device(void*, const void*, void* x_next) = 0;
-  virtual int closed_loop(void*, void*, int, const void* ptau_seq = nullptr, int per_instance = 0) = 0;
+  virtual int closed_loop(void* x, void* u, int n_ticks, const cgm::LoopSeqs& seqs) = 0;
   virtual double time() const = 0;
   virtual int get_state(double*, void*, void*) = 0;
   virtual int set_state(double, const void*, const void*) = 0;

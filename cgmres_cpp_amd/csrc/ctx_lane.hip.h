@@ -126,21 +126,29 @@ struct CtxLane final : cgmres_hip_ctx {
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
   }
-  int closed_loop(void* x, void* u, int n_ticks, const void* ptau_seq, int per_instance) override {
+  int closed_loop(void* x, void* u, int n_ticks, const LoopSeqs& sq) override {
     HIP_TRY(hipSetDevice(cfg.device));
     if (!u || !x) return fail(CGMRES_HIP_EINVAL, "closed_loop: null pointer");
-    const int all = np * (cfg.dv + 1);
+    const int all = np * (cfg.dv + 1), per_instance = sq.ptau_per_instance;
     const size_t per_tick = size_t(per_instance ? cfg.batch : 1) * all;
-    for (int i = 0; i < n_ticks; ++i) {
-      if (ptau_seq && all) {  // set_ptau before this tick (cgmres.hpp:36-39), device to device
+    // plant inputs (cgmres_hip_closed_loop_device_ex): d and v, [n_ticks][batch or 1][nx]
+    const T *dseq = static_cast<const T*>(sq.dist), *mseq = static_cast<const T*>(sq.meas);
+    const size_t d_tick = size_t(sq.dist_per_instance ? cfg.batch : 1) * nx, m_tick = size_t(sq.meas_per_instance ? cfg.batch : 1) * nx;
+    P.dist_inst = sq.dist_per_instance ? nx : 0, P.meas_inst = sq.meas_per_instance ? nx : 0;
+    int rc = 0;
+    for (int i = 0; i < n_ticks && !rc; ++i) {
+      if (sq.ptau && all) {  // set_ptau before this tick (cgmres.hpp:36-39), device to device
         dim3 grid((cfg.batch + 255) / 256, all);
-        to_element_major<T><<<grid, 256, 0, stream>>>(P.ptau, static_cast<const T*>(ptau_seq) + i * per_tick, cfg.batch,
+        to_element_major<T><<<grid, 256, 0, stream>>>(P.ptau, static_cast<const T*>(sq.ptau) + i * per_tick, cfg.batch,
                                                        ldb, all, !per_instance);
         HIP_TRY(hipGetLastError());
       }
-      if (int rc = launch_tick(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x))) return rc;
+      P.dist = dseq ? dseq + size_t(i) * d_tick : nullptr;
+      P.meas = mseq ? mseq + size_t(i) * m_tick : nullptr;
+      rc = launch_tick(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x));
     }
-    return 0;
+    P.dist = nullptr, P.meas = nullptr;  // control() and the hooks take neither
+    return rc;
   }
 
   double time() const override { return double(t); }

@@ -47,6 +47,7 @@ struct CtxWg final : cgmres_hip_ctx {
   // (WgCtx::load_vec).  get_krylov un-permutes accordingly.
   bool v_by_stage = false;
   int* perm_dev = nullptr;   // placement of the next fused launch (bin_by_count_kernel)
+  PlantSeqs<T>* pin_dev = nullptr;  // plant inputs of the next fused launch (closed_loop)
   bool have_counts = false;  // n_ax holds the counts of a finished tick
   using Tr = WgTraits<M, T>;
   const char* variant_name() const override { return wg_variant_name(plan); }
@@ -121,7 +122,7 @@ struct CtxWg final : cgmres_hip_ctx {
         (rc = dalloc(&P.pT, plan.k.lean ? wgs * (cfg.dv + 1) * (np ? np : 1) * ipw : 1)) ||
         (rc = dalloc(&P.park, wgs * ipw * P.Lv)) ||  // (every kernel family parks the solution vector now)
         (rc = dalloc(&P.n_ax, B)) || (rc = dalloc(&P.reason, B)) || (rc = dalloc(&x_dev, B * nx)) ||
-        (rc = dalloc(&u_dev, B * nu)) || (rc = dalloc(&perm_dev, B)))
+        (rc = dalloc(&u_dev, B * nu)) || (rc = dalloc(&perm_dev, B)) || (rc = dalloc(&pin_dev, 1)))
       return rc;
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
@@ -247,27 +248,46 @@ struct CtxWg final : cgmres_hip_ctx {
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
   }
-  int closed_loop(void* x, void* u, int n_ticks, const void* ptau_seq, int per_instance) override {
+  int closed_loop(void* x, void* u, int n_ticks, const LoopSeqs& sq) override {
     HIP_TRY(hipSetDevice(cfg.device));
     if (!u || !x) return fail(CGMRES_HIP_EINVAL, "closed_loop: null pointer");
-    const int all = np * (cfg.dv + 1);
-    const T* seq = all ? static_cast<const T*>(ptau_seq) : nullptr;
+    const int all = np * (cfg.dv + 1), per_instance = sq.ptau_per_instance;
+    const T* seq = all ? static_cast<const T*>(sq.ptau) : nullptr;
     const size_t per_tick = size_t(per_instance ? cfg.batch : 1) * all;
     P.pseq_tick = per_tick, P.pseq_inst = per_instance ? all : 0;
-    int rc = 0;
-    for (int i = 0; i < n_ticks && !rc; i += CGM_FUSE_MAX) {
-      const int n = n_ticks - i < CGM_FUSE_MAX ? n_ticks - i : CGM_FUSE_MAX;
-      P.ptau_seq = seq ? seq + size_t(i) * per_tick : nullptr;  // the kernel reloads ptau at the top of every tick
-      if (plan.binning && have_counts) {
-        bin_by_count_kernel<0><<<1, 1024, 0, stream>>>(perm_dev, P.n_ax, cfg.batch, cfg.k_max);
-        HIP_TRY(hipGetLastError());
-        P.perm = perm_dev;
+    // plant inputs (cgmres_hip_closed_loop_device_ex): d and v, [n_ticks][batch or 1][nx]
+    PlantSeqs<T> ps{static_cast<const T*>(sq.dist), static_cast<const T*>(sq.meas),
+                    size_t(sq.dist_per_instance ? cfg.batch : 1) * nx, size_t(sq.meas_per_instance ? cfg.batch : 1) * nx,
+                    sq.dist_per_instance ? nx : 0, sq.meas_per_instance ? nx : 0};
+    const bool plant_in = ps.dist || ps.meas;
+    // (a lambda, so that a failed launch check leaves through the line below it, which takes the per-launch pointers off
+    // the handle: a later control() must not meet a stale sequence or PlantSeqs record)
+    auto launches = [&]() -> int {
+      for (int i = 0; i < n_ticks; i += CGM_FUSE_MAX) {
+        const int n = n_ticks - i < CGM_FUSE_MAX ? n_ticks - i : CGM_FUSE_MAX;
+        P.ptau_seq = seq ? seq + size_t(i) * per_tick : nullptr;  // the kernel reloads ptau at the top of every tick
+        if (plant_in) {  // this launch's rows, through the device-resident record the kernel reads (stream-ordered)
+          PlantSeqs<T> q = ps;
+          q.dist = ps.dist ? ps.dist + size_t(i) * ps.dist_tick : nullptr;
+          q.meas = ps.meas ? ps.meas + size_t(i) * ps.meas_tick : nullptr;
+          set_plant_seqs_kernel<T><<<1, 1, 0, stream>>>(pin_dev, q);
+          HIP_TRY(hipGetLastError());
+          P.pin = pin_dev;
+        }
+        if (plan.binning && have_counts) {
+          bin_by_count_kernel<0><<<1, 1024, 0, stream>>>(perm_dev, P.n_ax, cfg.batch, cfg.k_max);
+          HIP_TRY(hipGetLastError());
+          P.perm = perm_dev;
+        }
+        const int rc = launch_ticks(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x), n);
+        P.perm = nullptr;
+        have_counts = true;
+        if (rc) return rc;
       }
-      rc = launch_ticks(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x), n);
-      P.perm = nullptr;
-      have_counts = true;
-    }
-    P.ptau_seq = nullptr;
+      return 0;
+    };
+    const int rc = launches();
+    P.ptau_seq = nullptr, P.pin = nullptr, P.perm = nullptr;  // control() and the hooks take none of them
     if (!rc && seq && n_ticks > 0) {  // the handle keeps the last tick's ptau, as set_ptau would (cgmres.hpp:36-39)
       replicate_rows_im<T><<<dim3(4, cfg.batch), 256, 0, stream>>>(P.ptau, all, seq + size_t(n_ticks - 1) * per_tick,
                                                                     cfg.batch, all, 1, !per_instance);

@@ -32,6 +32,10 @@ struct TickParams {
   const T* x_in;
   T* u_out;
   T* x_next;  // non-null: also write the plant's forward-Euler step x + dxdt(x,u)*dt here
+  // this tick's plant inputs (cgmres_hip_closed_loop_device_ex): [NX] at b * stride, null = absent.  meas: the controller
+  // is shown x + v; dist: x_next = (x + dxdt(x,u)*dt) + d, dxdt at the true state x
+  const T *dist, *meas;
+  int dist_inst, meas_inst;
 };
 
 enum FOut { F_PLAIN = 0, F_RHS = 1, F_AX = 2 };
@@ -304,6 +308,10 @@ __global__ __launch_bounds__(64) void tick_lane_kernel(TickParams<T> P) {
   T x[M::NX];
 #pragma unroll
   for (int i = 0; i < M::NX; ++i) x[i] = P.x_in[size_t(b) * M::NX + i];
+  if (P.meas) {
+#pragma unroll
+    for (int i = 0; i < M::NX; ++i) x[i] = x[i] + P.meas[size_t(b) * P.meas_inst + i];
+  }
   prepare_lane<M, T>(P, ld, A, x);
   int n_ax = 0;
   const int reason = gmres_lane<M, T>(P, ld, A, A.dUdt, A.bvec, &n_ax);  // cgmres.hpp:99
@@ -320,9 +328,17 @@ __global__ __launch_bounds__(64) void tick_lane_kernel(TickParams<T> P) {
     T f[M::NX], tr[M::NC > 0 ? M::NC : 1];
     typename M::Math mc;
     mc.init();
+    if (P.meas) {  // x holds the measurement: the plant moves the true state
+#pragma unroll
+      for (int i = 0; i < M::NX; ++i) x[i] = P.x_in[size_t(b) * M::NX + i];
+    }
     state_eq<M, T>(f, x, u, tr, mc, A.ptau, ld, 0);
 #pragma unroll
-    for (int i = 0; i < M::NX; ++i) P.x_next[size_t(b) * M::NX + i] = x[i] + f[i] * P.dt;
+    for (int i = 0; i < M::NX; ++i) {
+      T xn = x[i] + f[i] * P.dt;
+      if (P.dist) xn = xn + P.dist[size_t(b) * P.dist_inst + i];
+      P.x_next[size_t(b) * M::NX + i] = xn;
+    }
   }
 }
 

@@ -409,6 +409,11 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(VLDS ?
     }
 #pragma unroll
     for (int c = 0; c < NX; ++c) xs[c] = P.x_in[size_t(b) * NX + c];
+    if (__builtin_expect(P.pin != nullptr, 0) && P.pin->meas) {  // y_0 = x_0 + v_0 of this launch: xs is what the controller sees, the true state stays in x_in
+      const T* v0 = P.pin->meas + size_t(b) * P.pin->meas_inst;
+#pragma unroll
+      for (int c = 0; c < NX; ++c) xs[c] = xs[c] + v0[c];
+    }
   }
   int n_ax = 0, reason = 0, ksolve = 0;
   T xh[NX];
@@ -993,19 +998,58 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(VLDS ?
       }
     }
     if (P.x_next) {  // plant step of the example main loop (<example>/main.cpp:71-73)
-      T f[NX], tr[NC > 0 ? NC : 1];
-      if constexpr (SERIAL)
-        dxdt_p0(f, xs, unew);  // (the example's plant = the model's own state equation, p of stage 0)
+      // One body, compiled twice: the copy with the plant inputs of cgmres_hip_closed_loop_device_ex (d, v) runs only
+      // with P.pin set, and the default copy holds none of their statements, so the register allocation of a kernel
+      // that is given neither is that of a kernel without the feature (tools/isa_summary.py: spills, scratch).
+      auto plant = [&](auto with_inputs) {
+        constexpr bool INPUTS = decltype(with_inputs)::value;
+        T f[NX], tr[NC > 0 ? NC : 1];
+        const T *dk = nullptr, *vk = nullptr;
+        bool noisy = false;
+        if constexpr (INPUTS) {
+          const PlantSeqs<T> ps = *P.pin;
+          noisy = ps.meas != nullptr;
+          if (ps.dist) dk = ps.dist + size_t(tk) * ps.dist_tick + size_t(b) * ps.dist_inst;
+          if (noisy && !last) vk = ps.meas + size_t(tk + 1) * ps.meas_tick + size_t(b) * ps.meas_inst;
+          if (noisy) {
+            // xs holds y = x + v; the true state lives in the caller's buffer (x_in == x_next in the closed loop), written
+            // by lanes < NX of THIS wave at the end of the previous tick: no register carries it across the solve.  The two
+            // fences are no release / acquire pair of the memory model (no atomic sits between them): writer and readers
+            // are lanes of one wave, in program order, and the fences only drain the wave's outstanding stores before its
+            // loads issue and keep the compiler from moving either across.  Not a pattern for data passed between waves.
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+            for (int c = 0; c < NX; ++c) xs[c] = P.x_next[size_t(b) * NX + c];
+          }
+        }
+        if constexpr (SERIAL)
+          dxdt_p0(f, xs, unew);  // (the example's plant = the model's own state equation, p of stage 0)
+        else
+          M::dxdt(f, xs, unew, tr, mc);
+#pragma unroll
+        for (int c = 0; c < NX; ++c) xs[c] = xs[c] + f[c] * P.dt;
+        if (dk) {
+#pragma unroll
+          for (int c = 0; c < NX; ++c) xs[c] = xs[c] + dk[c];
+        }
+        if ((last || noisy) && lane < NX) {
+          T r = xs[0];
+#pragma unroll
+          for (int q = 1; q < NX; ++q) r = lane == q ? xs[q] : r;
+          P.x_next[size_t(b) * NX + lane] = r;
+        }
+        if constexpr (INPUTS) {
+          if (noisy) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+          if (vk) {  // what the next tick's controller sees
+#pragma unroll
+            for (int c = 0; c < NX; ++c) xs[c] = xs[c] + vk[c];
+          }
+        }
+      };
+      if (__builtin_expect(P.pin != nullptr, 0))
+        plant(std::true_type{});
       else
-        M::dxdt(f, xs, unew, tr, mc);
-#pragma unroll
-      for (int c = 0; c < NX; ++c) xs[c] = xs[c] + f[c] * P.dt;
-      if (last && lane < NX) {
-        T r = xs[0];
-#pragma unroll
-        for (int q = 1; q < NX; ++q) r = lane == q ? xs[q] : r;
-        P.x_next[size_t(b) * NX + lane] = r;
-      }
+        plant(std::false_type{});
     }
   }
   CGM_STAMP(0, 11);

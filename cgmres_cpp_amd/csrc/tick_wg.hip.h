@@ -60,6 +60,22 @@ static_assert(CGM_FUSE_MAX == 10, "WgParams::dtau_tab");
 
 enum WgMode { WG_TICK = 0, WG_HOOK_F = 1, WG_HOOK_PREPARE = 2, WG_HOOK_AX = 3, WG_HOOK_GMRES = 4 };
 
+// Plant inputs of one fused launch, indexed like WgParams::ptau_seq with [NX] per instance, by the caller's instance index
+// (never by the placement slot): dist = process disturbance d, x_{k+1} = (x_k + f(x_k, u_k) dt) + d_k; meas = measurement
+// noise v, the controller is shown y_k = x_k + v_k.  Either may be null.  With meas the TRUE state x_k lives in the
+// caller's x buffer (x_in == x_next, written every tick) and the on-chip copy holds y_k.
+template <class T>
+struct PlantSeqs {
+  const T* dist;
+  const T* meas;
+  size_t dist_tick, meas_tick;  // elements per tick
+  int dist_inst, meas_inst;     // elements per instance (0 = one row broadcast to every instance)
+};
+template <class T>
+__global__ void set_plant_seqs_kernel(PlantSeqs<T>* dst, PlantSeqs<T> v) {
+  *dst = v;
+}
+
 template <class T>
 struct WgParams {
   int B, dv, kmax, L, Lp, Lg, Lv, Pp, Hp, fh_hbm, lds_bytes;  // fh_hbm: F(U,x+hf,t+h) is kept in HBM only (P.Fh), see WgLds
@@ -84,6 +100,9 @@ struct WgParams {
   const T* ptau_seq;
   size_t pseq_tick;
   int pseq_inst;
+  // plant inputs of the fused loop (cgmres_hip_closed_loop_device_ex): null = none.  Behind ONE pointer to a device-resident
+  // record, so that the kernels of the default path carry two more scalar registers and nothing else
+  const PlantSeqs<T>* pin;
   // instance-major HBM state
   T *U, *dUdt, *Fh, *V, *xdxh, *ptau;  // [B][Lg], [B][Lg], [B][Lg], [B][kmax+1][Lv], [B][NX], [B][NP*(dv+1)]
   T* kry;                              // [B][KS]: H (k1*k1 col-major) | rho (k1) | g (3*kmax)
@@ -490,7 +509,10 @@ struct WgCtx {
         const int q = r + 16 * n;
         preg[n] = q < np_all ? P.ptau[size_t(b) * np_all + q] : T(0);
       }
-      if (r < M::NX && P.x_in) xreg = P.x_in[size_t(b) * M::NX + r];
+      if (r < M::NX && P.x_in) {
+        xreg = P.x_in[size_t(b) * M::NX + r];
+        if (__builtin_expect(P.pin != nullptr, 0) && P.pin->meas) xreg = xreg + P.pin->meas[size_t(b) * P.pin->meas_inst + r];  // y_0 = x_0 + v_0 of this launch
+      }
     }
     if constexpr (U_IN_REGS) {
 #pragma unroll
@@ -2813,6 +2835,17 @@ __global__ __launch_bounds__(IPW * 16) __attribute__((amdgpu_waves_per_eu(LEAN ?
     }
     if (P.x_next) {  // plant step of the example main loop (<example>/main.cpp:71-73)
       __syncthreads();
+      // Plant inputs of cgmres_hip_closed_loop_device_ex (d, v): two cold blocks around the plant step, which itself stays
+      // statement for statement what it is without them.  They talk to it through S.xs alone, each sweep lane reading
+      // back what it wrote itself, so that a kernel that is given neither input keeps (within a few registers,
+      // tools/isa_summary.py) the allocation it has without the feature.  A shared block with selects did not.
+      const bool inputs = __builtin_expect(P.pin != nullptr, 0) && C.sweep_lane;
+      if (inputs && P.pin->meas) {
+        // S.xs holds y = x + v: the plant moves the TRUE state, which is in the caller's buffer, last written by this lane
+        const T* xt = P.x_next + size_t(C.bi) * M::NX;
+#pragma unroll
+        for (int c = 0; c < M::NX; ++c) C.S.xs[c * IPW + C.tid] = xt[c];
+      }
       if (C.sweep_lane) {
         const int i = C.tid;
         T x[M::NX], u[M::NU], f[M::NX], tr[M::NC > 0 ? M::NC : 1];
@@ -2826,6 +2859,20 @@ __global__ __launch_bounds__(IPW * 16) __attribute__((amdgpu_waves_per_eu(LEAN ?
           const T xn = x[c] + f[c] * P.dt;
           if (last) P.x_next[size_t(C.bi) * M::NX + c] = xn;
           C.S.xs[c * IPW + i] = xn;
+        }
+      }
+      if (inputs) {  // x_{k+1} = (x_k + f dt) + d_k, kept in the caller's buffer every tick when v is given; S.xs = x_{k+1} + v_{k+1}
+        const int i = C.tid;
+        const PlantSeqs<T> q = *P.pin;
+        const T* dk = q.dist ? q.dist + size_t(tk) * q.dist_tick + size_t(C.bi) * q.dist_inst : nullptr;
+        const T* vk = q.meas && !last ? q.meas + size_t(tk + 1) * q.meas_tick + size_t(C.bi) * q.meas_inst : nullptr;
+#pragma unroll
+        for (int c = 0; c < M::NX; ++c) {
+          T xn = C.S.xs[c * IPW + i];
+          if (dk) xn = xn + dk[c];
+          if (last || q.meas) P.x_next[size_t(C.bi) * M::NX + c] = xn;
+          if (vk) xn = xn + vk[c];
+          C.S.xs[c * IPW + i] = xn;  // what the next tick's controller sees
         }
       }
     }

@@ -65,6 +65,12 @@ class CgmresBatch {
     cgmres_detail::check(cgmres_hip_closed_loop_device_ptau(handle_, x_dev, u_dev, n_ticks, ptau_seq_dev, per_instance ? 1 : 0),
                          "closed_loop_device_ptau");
   }
+  // the same loop with a process disturbance and / or a measurement noise sequence (and, optionally, the ptau sequence):
+  // y_k = x_k + v_k, u_k = control(y_k), x_{k+1} = (x_k + f(x_k, u_k)*dt) + d_k — cgmres_hip_closed_loop_device_ex.
+  // `in.struct_size` must be sizeof(cgmres_hip_loop_inputs); the sequences are device pointers
+  void closed_loop_device(double* x_dev, double* u_dev, int32_t n_ticks, const cgmres_hip_loop_inputs& in) {
+    cgmres_detail::check(cgmres_hip_closed_loop_device_ex(handle_, x_dev, u_dev, n_ticks, &in), "closed_loop_device_ex");
+  }
   void synchronize() { cgmres_detail::check(cgmres_hip_synchronize(handle_), "synchronize"); }
 
   // Arnoldi mat-vecs executed and exit reason (CGMRES_HIP_EXIT_*) per instance for the last tick

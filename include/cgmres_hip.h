@@ -31,8 +31,10 @@ extern "C" {
 #endif
 
 /* 2: cgmres_hip_config gained `flags`; plugin contract (the model plugin picks the mapping, closed loop with a reference
- *    sequence); exit reason CGMRES_HIP_EXIT_NONFINITE.  A plugin or binding built against version 1 is rejected. */
-#define CGMRES_HIP_ABI_VERSION 2
+ *    sequence); exit reason CGMRES_HIP_EXIT_NONFINITE.  A plugin or binding built against version 1 is rejected.
+ * 3: plugin contract (closed loop with a process-disturbance and a measurement-noise sequence:
+ *    cgmres_hip_closed_loop_device_ex).  A plugin or binding built against version 2 is rejected. */
+#define CGMRES_HIP_ABI_VERSION 3
 
 /* problem definitions compiled into the library (reference <example>/model.hpp) */
 enum {
@@ -188,6 +190,33 @@ int cgmres_hip_closed_loop_device(cgmres_hip_handle h, void* x_dev, void* u_dev,
  * With dim_p = 0 the sequence is ignored.  Asynchronous on the handle's stream. */
 int cgmres_hip_closed_loop_device_ptau(cgmres_hip_handle h, void* x_dev, void* u_dev, int32_t n_ticks,
                                        const void* ptau_seq_dev, int per_instance);
+/* The same loop (<example>/main.cpp:63-73) with a plant that is NOT the controller's nominal model run on the
+ * controller's own state: a process disturbance d and a measurement noise v, both optional, per tick and per instance.
+ * x_k is the TRUE plant state; x_dev holds x_0 on entry.  For tick k = 0 .. n_ticks-1 of one call
+ *     y_k     = x_k + v_k                      (v absent: y_k = x_k)
+ *     u_k     = control(y_k)                   (cgmres.hpp:78-110 unchanged: x_dxh etc. are built from y_k)
+ *     x_{k+1} = (x_k + f(x_k, u_k)*dt) + d_k   (d absent: the expression of cgmres_hip_closed_loop_device; f = the
+ *                                               model's dxdt at the TRUE state, with p of stage 0)
+ * On return x_dev = x_n (true state) and u_dev = u_{n-1}; time, status, Krylov arrays, F_dxh_h / x_dxh are as after the
+ * same ticks of cgmres_hip_closed_loop_device, the handle's ptau is the last tick's as after ..._ptau.
+ * dist_seq_dev / meas_seq_dev are device arrays of the handle's dtype, [n_ticks][batch][dim_x] when the matching
+ * *_per_instance is 1, [n_ticks][dim_x] (one vector broadcast to every instance) when it is 0, indexed by the caller's
+ * instance index.  The library draws no random numbers: a Monte-Carlo study brings its own.  The ticks stay fused.
+ * in == NULL or all three pointers NULL: exactly cgmres_hip_closed_loop_device; only ptau_seq_dev set: exactly
+ * ..._ptau (with dim_p = 0 the ptau sequence is ignored).  n_ticks == 0 does nothing.  CGMRES_HIP_EINVAL: struct_size
+ * other than sizeof(cgmres_hip_loop_inputs), a *_per_instance outside {0, 1}, n_ticks < 0, a dist / meas array whose
+ * byte range overlaps x_dev or u_dev (the alias guard of cgmres_hip_control).  Asynchronous on the handle's stream. */
+typedef struct cgmres_hip_loop_inputs {
+  int32_t struct_size;        /* sizeof(cgmres_hip_loop_inputs); anything else: CGMRES_HIP_EINVAL */
+  int32_t ptau_per_instance;  /* 0 / 1, as in cgmres_hip_closed_loop_device_ptau */
+  int32_t dist_per_instance;  /* 0 / 1 */
+  int32_t meas_per_instance;  /* 0 / 1 */
+  const void* ptau_seq_dev;   /* NULL: the handle's ptau on every tick */
+  const void* dist_seq_dev;   /* d: NULL = none */
+  const void* meas_seq_dev;   /* v: NULL = none */
+} cgmres_hip_loop_inputs;
+int cgmres_hip_closed_loop_device_ex(cgmres_hip_handle h, void* x_dev, void* u_dev, int32_t n_ticks,
+                                     const cgmres_hip_loop_inputs* in);
 int cgmres_hip_synchronize(cgmres_hip_handle h);
 
 /* ---- state: the private members of Cgmres (cgmres.hpp:195-202) and Gmres (gmres.hpp:120-124) ------ */
