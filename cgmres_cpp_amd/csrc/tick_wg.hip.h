@@ -145,7 +145,7 @@ __device__ long long g_cgm_stamps[64];
 // once at the end of the kernel: a global atomic per stamp queues behind the basis-row loads in flight and made the
 // stamps after them look ~1.5 k cycles long.
 __device__ __forceinline__ long long* cgm_stamp_lds() {
-  __shared__ long long acc[66];  // [0..31] cycles, [32..63] visits, [64] last stamp
+  __shared__ long long acc[66];  // [0..31] cycles, [32..63] visits, [64] last stamp (ids 28, 29: see cgm_stamp_flush)
   return acc;
 }
 __device__ __forceinline__ void cgm_stamp(int id) {
@@ -169,8 +169,14 @@ __device__ __forceinline__ void cgm_stamp_flush() {
     for (int i = 0; i < 28; ++i) g_cgm_stamps[i] += acc[i], g_cgm_stamps[32 + i] += acc[32 + i];
     g_cgm_stamps[28] += (long long)__builtin_amdgcn_s_memrealtime() - g_cgm_stamps[30];
     g_cgm_stamps[29] += (long long)__builtin_amdgcn_s_memtime() - g_cgm_stamps[31];
+    // ids 28 and 29 (the split of the Gram-Schmidt rounds): the buffer keeps its 64 words, their cycles go to the unused
+    // words 60, 61 and their visits to 62, 63
+    for (int i = 0; i < 2; ++i) g_cgm_stamps[60 + i] += acc[28 + i], g_cgm_stamps[62 + i] += acc[60 + i];
   }
 }
+// s_waitcnt that leaves the `vm` youngest vector-memory operations in flight (gfx9 encoding: vmcnt in bits 3:0 and 15:14,
+// the other counters untouched)
+constexpr int cgm_vmcnt_imm(int vm) { return 0x0F70 | (vm & 15) | ((vm >> 4) << 14); }
 #define CGM_STAMP(ctx, id) cgm_stamp(id)
 // the same behind the LDS operations in flight: what the stamp closes is a fetch, whose cost is the round trip and not the issue
 #define CGM_STAMP_LDS(ctx, id) (__extension__({ asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); cgm_stamp(id); }))
@@ -2286,6 +2292,41 @@ struct WgCtx {
     // vectors, with the solution vector parked in HBM for the duration of the loop like the long-vector kernels do.
     constexpr int NKEEP = (!LEAN && MAXM <= 10) ? 2 : 0;
     T vkeep[NKEEP > 0 ? NKEEP : 1][NVEC];
+    // Row-Newton kernel: the ring rounds and the ring part of the x update are ONE loop each instead of twelve
+    // straight-line cases — NBUF rounds per trip with static buffer indices, every buffer refilled unconditionally right
+    // after its round with the row index clamped to the last needed row (the streaming loops' technique, so the waits
+    // stay s_waitcnt vmcnt(N > 0)), fewer than NBUF remaining rounds in a peeled tail.  The look-ahead leaves up to NBUF
+    // requests nobody consumes: those of the rounds are drained by the s_waitcnt vmcnt(0) in front of the next
+    // iteration's requests (request_rows, at the loop top in this form: no sweep inherits them; an explicit drain behind
+    // the rounds was measured, 86.6 vs 86.1 us per tick), those of the x update where its loop ends.  Same operations in
+    // the same order per element and per round.  A property of the kernel (template-selected): the other instantiations
+    // keep their text.  (CGM_GS_COMPACT=0: A/B builds of the twelve-case form from this source.)
+#ifndef CGM_GS_COMPACT
+#define CGM_GS_COMPACT 1
+#endif
+    constexpr bool COMPACT = NWT == 1 && NKEEP > 0 && CGM_GS_COMPACT != 0;
+    // Diagnostic build: the Gram-Schmidt stamp split in three — 28 closes an explicit wait for the ring row a round is
+    // about to use (the `younger` rows requested after it stay in flight, as in the product build), 29 the ring round
+    // itself (arithmetic, instruction fetch, refill request), 7 keeps the register rounds and the norm.
+    auto stamp_row_wait = [&](int younger) {
+#ifdef CGM_STAMPS
+      if constexpr (NWT == 1) {
+        CGM_STAMP(*this, 7);
+        constexpr int LPR = NVEC / 2;  // 16-byte loads per row and lane
+        switch (younger) {
+          case 0: __builtin_amdgcn_s_waitcnt(cgm_vmcnt_imm(0)); break;
+          case 1: __builtin_amdgcn_s_waitcnt(cgm_vmcnt_imm(LPR)); break;
+          default: __builtin_amdgcn_s_waitcnt(cgm_vmcnt_imm(2 * LPR)); break;
+        }
+        CGM_STAMP(*this, 28);
+      }
+#endif
+    };
+    auto stamp_ring_round = [&] {
+#ifdef CGM_STAMPS
+      if constexpr (NWT == 1) CGM_STAMP(*this, 29);
+#endif
+    };
     // workgroup-uniform; longer bases use the plain streaming loop.  So does the lean plan: with 256 registers per wave the
     // twelve straight-line copies of the rounds push everything that lives across them (U, the sweep constants) into
     // scratch — in every block of the kernel, executed or not.
@@ -2392,9 +2433,16 @@ struct WgCtx {
       auto request_rows = [&]() {
         if (preload && active) {
           __builtin_amdgcn_s_waitcnt(0x0F70);
+          if constexpr (COMPACT) {
+            if (k > NKEEP) {  // (all NBUF buffers or none: buffers past the last needed row re-read it)
+#pragma unroll
+              for (int i = 0; i < NBUF; ++i) load_vec(vbuf[i], vrow(i + NKEEP < k ? i + NKEEP : k - 1));
+            }
+          } else {
 #pragma unroll
           for (int i = 0; i < NBUF; ++i)
             if (i + NKEEP < k) load_vec(vbuf[i], vrow(i + NKEEP));
+          }
         }
       };
       if (NWT == 0 && tid >= 64) request_rows();
@@ -2407,14 +2455,22 @@ struct WgCtx {
       };
       if constexpr (NWT != 0) {
         CGM_STAMP(*this, 3);
-        // (the basis rows are requested between the Newton iterations and the costate scans: early enough to arrive
-        // behind the scans, late enough that their registers are not live across the iterations, where the register
-        // file is fullest — requested before the sweep they sit in AGPRs and every use in the rounds below is a copy)
+        // (twelve-case form of the rounds: the basis rows are requested between the Newton iterations and the costate
+        // scans: early enough to arrive behind the scans, late enough that their registers are not live across the
+        // iterations, where the register file is fullest — requested before the sweep they sit in AGPRs and every use in
+        // the rounds below is a copy)
         if constexpr (NWT == 2) {
           request_rows();  // (a light sweep: the rows may be in flight across it)
           row_affine_sweep<F_AX>(S.xh, dtau_h, S.W + inst * P.Lp, S.W, active);
         } else {
-          row_newton_sweep<F_AX>(dtau_h, vcur, w, active, request_rows);  // :48  w <- A v_k, registers to registers
+          if constexpr (COMPACT) {
+            // (compact rounds: the ring sits in AGPRs whichever way — requested here, a whole sweep ahead, the first NBUF
+            // rows have arrived when their rounds come: 86.5 vs 87.6 us per tick, profiles/r07_gs_ab.json)
+            request_rows();
+            row_newton_sweep<F_AX>(dtau_h, vcur, w, active, [] {});  // :48  w <- A v_k, registers to registers
+          } else {
+            row_newton_sweep<F_AX>(dtau_h, vcur, w, active, request_rows);
+          }
         }
         CGM_STAMP(*this, 6);
       } else {
@@ -2446,6 +2502,31 @@ struct WgCtx {
           if (r == 0) Hk[i] = hik;
         };
         if (preload) {
+          if constexpr (COMPACT) {
+#pragma unroll
+            for (int i = 0; i < NKEEP; ++i)
+              if (i < k) mgs_round(vkeep[i], i);
+            if (k > NKEEP) {
+              int i = NKEEP;
+              for (; i + NBUF <= k; i += NBUF) {
+#pragma unroll
+                for (int d = 0; d < NBUF; ++d) {
+                  stamp_row_wait(NBUF - 1);
+                  mgs_round(vbuf[d], i + d);
+                  const int nxt = i + d + NBUF;
+                  load_vec(vbuf[d], vrow(nxt < k ? nxt : k - 1));
+                  stamp_ring_round();
+                }
+              }
+#pragma unroll
+              for (int d = 0; d < NBUF - 1; ++d)
+                if (i + d < k) {
+                  stamp_row_wait(NBUF - 1 - d);
+                  mgs_round(vbuf[d], i + d);
+                  stamp_ring_round();
+                }
+            }
+          } else {
           // One straight-line instance per k: with no branch between a load and its use the compiler counts the
           // outstanding loads exactly (s_waitcnt vmcnt(2*MAXM) in the steady state instead of vmcnt(0)).
           auto rounds = [&](auto kc) {
@@ -2458,13 +2539,16 @@ struct WgCtx {
                   continue;
                 }
               }
+              stamp_row_wait(K - 1 - i < NBUF - 1 ? K - 1 - i : NBUF - 1);
               mgs_round(vbuf[(i - NKEEP) % NBUF], i);
               if (i + NBUF < K) load_vec(vbuf[(i - NKEEP) % NBUF], vrow(i + NBUF));
+              stamp_ring_round();
             }
           };
           switch (k) {
             CGM_KCASES(rounds)
             default: break;
+          }
           }
         } else {
           // (register-starved lean kernels: v_k is streamed back from its row like the older ones instead of being
@@ -2604,9 +2688,16 @@ struct WgCtx {
     // the first basis rows of the x update are requested before the (serial) back substitution
     T vbx[NBUF][NVEC];
     if (preload && valid && reason <= 1) {
+      if constexpr (COMPACT) {
+        if (ks > NKEEP) {
+#pragma unroll
+          for (int j = 0; j < NBUF; ++j) load_vec(vbx[j], vrow(j + NKEEP < ks ? j + NKEEP : ks - 1));
+        }
+      } else {
 #pragma unroll
       for (int j = 0; j < NBUF; ++j)
         if (j + NKEEP < ks) load_vec(vbx[j], vrow(j + NKEEP));
+      }
     }
     if (valid && reason <= 1) {
       // back substitution (gmres.hpp:100-107), column-oriented over the lanes of the row: lane j owns e_j; step i
@@ -2659,7 +2750,32 @@ struct WgCtx {
       T acc[NVEC];
 #pragma unroll
       for (int m = 0; m < NVEC; ++m) acc[m] = T(0.0);
-      if (preload) {  // same register ring as the Gram-Schmidt rounds
+      if (preload) {
+        if constexpr (COMPACT) {  // the Gram-Schmidt rounds' loop: keep rows, NBUF ring rounds per trip, tail, drain
+          auto axpy = [&](const T* vj, int j) {
+            const T yj = rhoi[j];
+#pragma unroll
+            for (int m = 0; m < NVEC; ++m) acc[m] += vj[m] * yj;
+          };
+#pragma unroll
+          for (int j = 0; j < NKEEP; ++j)
+            if (j < ks) axpy(vkeep[j], j);
+          if (ks > NKEEP) {
+            int j = NKEEP;
+            for (; j + NBUF <= ks; j += NBUF) {
+#pragma unroll
+              for (int d = 0; d < NBUF; ++d) {
+                axpy(vbx[d], j + d);
+                const int nxt = j + d + NBUF;
+                load_vec(vbx[d], vrow(nxt < ks ? nxt : ks - 1));
+              }
+            }
+#pragma unroll
+            for (int d = 0; d < NBUF - 1; ++d)
+              if (j + d < ks) axpy(vbx[d], j + d);
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // the look-ahead nobody consumes (see the Gram-Schmidt rounds)
+          }
+        } else {  // same register ring as the Gram-Schmidt rounds
         auto& vbuf = vbx;
         auto rounds = [&](auto kc) {
           constexpr int K = decltype(kc)::value;
@@ -2681,6 +2797,7 @@ struct WgCtx {
         switch (ks) {
           CGM_KCASES(rounds)
           default: break;
+        }
         }
       } else {
         // streaming form, SDEPTH rows in flight (see the Gram-Schmidt loop)

@@ -16,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "cgmres_cpp_amd", "csrc")
-TMP = "/tmp/asm"
+TMP = os.environ.get("ISA_TMP", "/tmp/asm")
 
 
 def compile_tu(src):
@@ -53,7 +53,9 @@ def scan(body):
     iteration (Gram-Schmidt rounds, Hessenberg column) and the stage loops of the preamble; depth >= 3 = the stage
     loops inside the Arnoldi loop (the critical path).  Loops that contain v_trig_preop_f64 (library
     sincos inlined) or a call (library sincos out of line, lean kernels) are the redo of a chunk whose arguments left
-    the fast trig range: counted separately as `slow`."""
+    the fast trig range: counted separately as `slow`.  Only a loop of depth >= 3 can be such a redo: the row-parallel
+    kernels (NWT) inline sincos straight into the Arnoldi loop (no stage loop around it), and there only the blocks that
+    hold the library path themselves are `slow` — the rest of the Arnoldi loop is `iter` like everywhere else."""
     blocks, cur = [], None
     for line in body.split("\n"):
         t = line.strip()
@@ -75,17 +77,18 @@ def scan(body):
         if not t or t.startswith("."):
             continue
         cur["ops"].append(t.split()[0])
-    slow_headers = {b["header"] for b in blocks
-                    if b["header"] and any(o in ("v_trig_preop_f64", "s_swappc_b64") for o in b["ops"])}
-    levels = {k: dict(n=0, scratch=0, acc=0) for k in ("tick", "iter", "stage", "slow", "outside")}
+    is_slow = lambda b: any(o in ("v_trig_preop_f64", "s_swappc_b64") for o in b["ops"])
+    slow_headers = {b["header"] for b in blocks if b["header"] and b["depth"] >= 3 and is_slow(b)}
+    levels = {k: dict(n=0, scratch=0, acc=0, lane=0) for k in ("tick", "iter", "stage", "slow", "outside")}
     loops = {}
     for b in blocks:
-        key = ("slow" if b["header"] in slow_headers else
+        key = ("slow" if b["header"] in slow_headers or (b["depth"] in (1, 2) and is_slow(b)) else
                "outside" if b["depth"] == 0 else "tick" if b["depth"] == 1 else "iter" if b["depth"] == 2 else "stage")
         sc = sum(o.startswith("scratch_") for o in b["ops"])
         ac = sum(o.startswith("v_accvgpr") for o in b["ops"])
         lv = levels[key]
         lv["n"] += len(b["ops"]); lv["scratch"] += sc; lv["acc"] += ac
+        lv["lane"] += sum(o.startswith(("v_readlane", "v_writelane")) for o in b["ops"])
         if key == "stage":
             l = loops.setdefault(b["header"], dict(n=0, scratch=0, acc=0, ds=0, vmem=0))
             l["n"] += len(b["ops"]); l["scratch"] += sc; l["acc"] += ac
@@ -118,7 +121,7 @@ def main():
              "Arnoldi loop (state / coefficient / costate sweeps: the critical path), `iter` = once per Arnoldi iteration",
              "(Gram-Schmidt rounds, Hessenberg column) and the preamble's stage loops, `tick` = once per control tick,",
              "`slow` = the library-sincos redo of a chunk of stages (arguments beyond the fast trig range; never taken in the benchmarks).",
-             "Entries are `scratch/acc` instruction counts (static).", "",
+             "Entries are `scratch/acc/lane` instruction counts (static; lane = v_readlane + v_writelane) of `instrs` instructions.", "",
              "| kernel | VGPR | AGPR | VGPR spill | SGPR spill | scratch B/lane | instrs | stage | iter | tick | slow |",
              "|---|---|---|---|---|---|---|---|---|---|---|"]
     detail = []
@@ -133,7 +136,7 @@ def main():
             lv, loops = scan(m.group(0))
             r = rm.get(name, {})
             short = re.sub(r"cgm::|void |\(cgm::WgParams<\w+>\)|\(cgm::LaneParams<\w+>\)", "", dm.get(name, name))
-            cell = lambda k: f"{lv[k]['scratch']}/{lv[k]['acc']}"
+            cell = lambda k: f"{lv[k]['scratch']}/{lv[k]['acc']}/{lv[k]['lane']} of {lv[k]['n']}"
             lines.append(f"| `{short}` | {r.get('vgpr')} | {r.get('agpr')} | {r.get('vgpr_spill')} | {r.get('sgpr_spill')} | "
                          f"{r.get('scratch')} | {sum(v['n'] for v in lv.values())} | {cell('stage')} | {cell('iter')} | "
                          f"{cell('tick')} | {cell('slow')} |")

@@ -55,6 +55,9 @@ names = {14: "loop top: before barrier_or", 15: "barrier_or (drains V row store)
          5: "sweep phase 2 (coeffs)", 18: "costate A: prologue (terminal costate, first fetches)", 19: "costate A: stage loop", 20: "costate A: tail stages",
          16: "costate A: four chunks side by side (record store when 18-20 are stamped)", 17: "costate: barrier",
          6: "sweep phase 3 (costate; B: boundaries + combine if chunk-parallel)", 7: "MGS rounds", 8: "norm+normalise+store",
+         # row-Newton kernel: "MGS rounds" split in three — 28 an explicit s_waitcnt for the ring row a round is about to use,
+         # 29 the ring round itself (arithmetic, instruction fetch, refill request), 7 the register rounds and the norm
+         28: "MGS rounds: wait for the ring row", 29: "MGS rounds: ring round (arithmetic + fetch)",
          21: "row Newton: x0/x2 scans", 22: "row Newton: iterations (visits = iterations)", 23: "row Newton: costate scans + out", 24: "row Newton: operands + stage coefficients",
          25: "row Newton: publish_direction (U + h v -> W)", 26: "row Newton: control fetch at the sweep head", 27: "row Newton: costate operand fetch",
          2: "row Newton: result row -> registers",
@@ -65,7 +68,12 @@ if c.variant == 4:  # the wave mapping's own stamp ids (tick_wave.hip.h)
              9: "r0", 6: "MGS rounds", 7: "norm+normalise+store", 8: "Hessenberg scalar", 13: "loop exit",
              10: "back-subst + x update"}
 tot = out[29]; wall = out[28]
+# the buffer keeps its 64 words: ids 28 and 29 have their cycles in words 60, 61 and their visits in 62, 63
+cyc = lambda k: out[k] if k < 28 else out[60 + k - 28]
+vis = lambda k: out[32 + k] if k < 28 else out[62 + k - 28]
+if c.variant == 4:
+    names = {k: n for k, n in names.items() if k < 28}
 print(f"ticks {N}: shader cycles/tick {tot/N:.0f}, wall {wall/N/100:.1f} us/tick -> clock {tot/wall*100/1e3:.2f} GHz")
 for k, n in names.items():
-    print(f"  {n:34s} {out[k]/N:10.0f} cyc/tick  {100*out[k]/tot:5.1f}%   ({out[32+k]/N:.0f} visits)")
-print("  accounted", sum(out[k] for k in names) / tot)
+    print(f"  {n:34s} {cyc(k)/N:10.0f} cyc/tick  {100*cyc(k)/tot:5.1f}%   ({vis(k)/N:.0f} visits)")
+print("  accounted", sum(cyc(k) for k in names) / tot)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Run on the GPU box (through gpurun):  bash tools/pmc_icache.sh [bench args]
 # Instruction-cache and instruction-fetch counters of the headline bench command, one rocprofv3 --pmc pass per group
-# (kernel trace only, as the pool requires).  Output: gpurun_out/icache/<group>/ + the available-counter list.
+# (a --pmc run carries no tracing of any kind: counters are collected in runs of their own).  Output: $O/g<n>/ + the available-counter list.
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
@@ -12,7 +12,8 @@ cat $O/names.txt
 i=0
 for grp in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES" "SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAIT_INST_ANY" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $grp -d $O/g$i -o pmc --output-format csv -- python3 $R/bench.py --steps 100 --warmup 20 --reps 1 --check-sample 0 --no-cpu-baseline --no-ref-mode "$@" > $O/g$i.log 2>&1 || { tail -5 $O/g$i.log; echo "group $i failed"; }
+  # (a group that fails ends the script: nothing more is started on a GPU that may have faulted)
+  timeout -k 10 300 rocprofv3 --pmc $grp -d $O/g$i -o pmc --output-format csv -- python3 $R/bench.py --steps 100 --warmup 20 --reps 1 --check-sample 0 --no-cpu-baseline --no-ref-mode "$@" > $O/g$i.log 2>&1 || { tail -5 $O/g$i.log; echo "group $i failed"; exit 1; }
 done
 python3 - <<'PY'
 import csv,glob,collections,os
