@@ -2055,8 +2055,8 @@ struct WgCtx {
   // leaves F unchanged bit for bit in the serial sweeps — A*d = 0 exactly, the reference's breakdown case
   // (gmres.hpp:63-65) — while Newton's fixed point agrees with the serial trajectory up to rounding only: gmres()
   // answers that case from this flag.
-  template <int MODE, class Mid>
-  __device__ __forceinline__ void row_newton_sweep(T dtau, const T* v, T* out, bool run, Mid&& mid) {
+  template <int MODE>
+  __device__ __forceinline__ void row_newton_sweep(T dtau, const T* v, T* out, bool run) {
     constexpr int NU = M::NU;
     static_assert(MODE == F_AX, "only the mat-vec of the Arnoldi loop");
     // (everything below derives from the thread index and is invariant over sweeps and ticks: left visible, the compiler
@@ -2216,7 +2216,6 @@ struct WgCtx {
         break;
       }
     }
-    mid();
     row_costate<MODE>(x0f, y1, x2f, y3, sd, cd, c1, u, dtau, out, tid_o);
   }
 
@@ -2252,6 +2251,70 @@ struct WgCtx {
     return en;
   }
 
+  // ---- the older Krylov basis rows, HBM -> registers (gmres(): the Gram-Schmidt rounds and x += V y) -----------------
+  // Rows V[first .. end-1] pass through DEPTH register buffers (the array's extent) with STATIC indices — no rotation by
+  // register moves: 20 v_mov per round, and a move would wait for the newest request.  A row is requested DEPTH rounds
+  // ahead and its buffer refilled right after its round, so each load has DEPTH-1 rounds (~1000 cycles) to arrive.
+
+  // One round of modified Gram-Schmidt (gmres.hpp:52-58): h(i,k) = <v_i, w> into Hk[i], w -= h(i,k) v_i
+  __device__ __forceinline__ void mgs_round(T* w, T* Hk, const T* vi, int i) const {
+    T pa = 0, pb = 0;  // two partial sums: the fp64 FMA chain is latency-bound (8 cycles/op dependent)
+#pragma unroll
+    for (int m = 0; m < NVEC; m += 2) {
+      pa += vi[m] * w[m];
+      if (m + 1 < NVEC) pb += vi[m + 1] * w[m + 1];
+    }
+    const T hik = row16_sum(pa + pb);
+#pragma unroll
+    for (int m = 0; m < NVEC; ++m) w[m] = w[m] - vi[m] * hik;
+    if (r == 0) Hk[i] = hik;
+  }
+  // One term of x += V y (gmres.hpp:110-111): acc += v_j y_j
+  __device__ __forceinline__ void axpy(T* acc, const T* y, const T* vj, int j) const {
+    const T yj = y[j];
+#pragma unroll
+    for (int m = 0; m < NVEC; ++m) acc[m] += vj[m] * yj;
+  }
+
+  // The clamped ring's first requests: all DEPTH buffers or none — a buffer past the last needed row re-reads that row.
+  template <int DEPTH>
+  __device__ __forceinline__ void ring_request(T (&buf)[DEPTH][NVEC], int first, int end) const {
+    if (end > first) {
+#pragma unroll
+      for (int d = 0; d < DEPTH; ++d) load_vec(buf[d], vrow(first + d < end ? first + d : end - 1));
+    }
+  }
+  // The clamped ring's rounds, after ring_request(buf, first, end): DEPTH rounds per trip, the remaining < DEPTH rounds
+  // in a peeled tail that finds its rows already requested.  A round is pre(rows requested after this one and still in
+  // flight), body(row, its index), the refill, post().
+  // The refill is UNCONDITIONAL, its row index clamped to the last needed row (the last trip re-reads it): a guard would
+  // be a branch between a load and its use, and the compiler then waits with vmcnt(0) — i.e. also for the row it has
+  // just requested, and nothing overlaps.  So the walk leaves up to DEPTH requests nobody consumes: see drain_stream.
+  // SCHED: a sched_barrier in front of every round keeps the requests TOGETHER and ahead of the arithmetic — under
+  // register pressure the scheduler otherwise sinks every load next to its use, one exposed round trip per element.
+  template <bool SCHED, int DEPTH, class Body, class Pre, class Post>
+  __device__ __forceinline__ void ring_walk(T (&buf)[DEPTH][NVEC], int first, int end, Body&& body, Pre&& pre, Post&& post) const {
+    int i = first;
+    for (; i + DEPTH <= end; i += DEPTH) {
+#pragma unroll
+      for (int d = 0; d < DEPTH; ++d) {
+        if constexpr (SCHED) __builtin_amdgcn_sched_barrier(0);
+        pre(DEPTH - 1);
+        body(buf[d], i + d);
+        const int nxt = i + d + DEPTH;
+        load_vec(buf[d], vrow(nxt < end ? nxt : end - 1));
+        post();
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < DEPTH - 1; ++d)
+      if (i + d < end) {
+        pre(DEPTH - 1 - d);
+        body(buf[d], i + d);
+        post();
+      }
+  }
+
   // Gmres::gmres (gmres.hpp:28-112).  In: x (registers `xv`), b (`bb`) and A*x0 (`ax0`), all in the row layout.
   // Out: xv updated.  All threads of the block must call this (it contains workgroup barriers).
   __device__ __forceinline__ void gmres(T* xv, const T* bb, const T* ax0) {
@@ -2261,16 +2324,8 @@ struct WgCtx {
     T* rhoi = S.rho + inst * k1;
     T* gi = S.g + inst * 3 * kmax;
     T vcur[NVEC], w[NVEC];
-    // Ring of NBUF register buffers for the older basis vectors: NBUF rows are requested before the sweep starts, and
-    // every buffer is refilled with row i+NBUF as soon as round i has consumed it, so each load has NBUF-1 rounds
-    // (~1000 cycles) to arrive.  Static buffer indices: one fully unrolled instance per iteration count (<= KRING).
-#define CGM_KCASE(f, n) \
-  case n:               \
-    f(std::integral_constant<int, n>{}); \
-    break;
-#define CGM_KCASES(f) \
-  CGM_KCASE(f, 1) CGM_KCASE(f, 2) CGM_KCASE(f, 3) CGM_KCASE(f, 4) CGM_KCASE(f, 5) CGM_KCASE(f, 6) CGM_KCASE(f, 7) \
-  CGM_KCASE(f, 8) CGM_KCASE(f, 9) CGM_KCASE(f, 10) CGM_KCASE(f, 11) CGM_KCASE(f, 12)
+    // Ring of NBUF register buffers for the older basis vectors of the full-plan kernels, bases up to KRING rows: the
+    // first NBUF rows are requested before the sweep starts.
     constexpr int NBUF = MAXM <= 10 ? 3 : 2, KRING = 12;
     // row buffers of the streaming loops (lean kernels, k_max > KRING).  Three buffers were measured as well: the 256-register
     // kernels then spill inside the Arnoldi loop (fp32 N = 100: 384 spilled VGPRs, cfg 5 526 -> 609 us/tick)
@@ -2292,19 +2347,57 @@ struct WgCtx {
     // vectors, with the solution vector parked in HBM for the duration of the loop like the long-vector kernels do.
     constexpr int NKEEP = (!LEAN && MAXM <= 10) ? 2 : 0;
     T vkeep[NKEEP > 0 ? NKEEP : 1][NVEC];
-    // Row-Newton kernel: the ring rounds and the ring part of the x update are ONE loop each instead of twelve
-    // straight-line cases — NBUF rounds per trip with static buffer indices, every buffer refilled unconditionally right
-    // after its round with the row index clamped to the last needed row (the streaming loops' technique, so the waits
-    // stay s_waitcnt vmcnt(N > 0)), fewer than NBUF remaining rounds in a peeled tail.  The look-ahead leaves up to NBUF
-    // requests nobody consumes: those of the rounds are drained by the s_waitcnt vmcnt(0) in front of the next
-    // iteration's requests (request_rows, at the loop top in this form: no sweep inherits them; an explicit drain behind
-    // the rounds was measured, 86.6 vs 86.1 us per tick), those of the x update where its loop ends.  Same operations in
-    // the same order per element and per round.  A property of the kernel (template-selected): the other instantiations
-    // keep their text.  (CGM_GS_COMPACT=0: A/B builds of the twelve-case form from this source.)
-#ifndef CGM_GS_COMPACT
-#define CGM_GS_COMPACT 1
-#endif
-    constexpr bool COMPACT = NWT == 1 && NKEEP > 0 && CGM_GS_COMPACT != 0;
+    // Row-Newton kernel: the ring rounds and the ring part of the x update are the clamped ring (ring_walk over the NBUF
+    // buffers, rows NKEEP on) instead of twelve straight-line cases.  Of the look-ahead nobody consumes, the requests of
+    // the rounds are drained by the s_waitcnt vmcnt(0) in front of the next iteration's requests (request_rows, at the
+    // loop top in this form: no sweep inherits them; an explicit drain behind the rounds was measured, 86.6 vs 86.1 us
+    // per tick), those of the x update where its walk ends.  A property of the kernel (template-selected).
+    constexpr bool COMPACT = NWT == 1 && NKEEP > 0;
+    // (lambdas here, not members like ring_walk: keep_rows and ring_cases capture vkeep, and cases_request stays next to
+    // the walker whose rows it requests)
+    auto keep_rows = [&](int n, auto&& body) {  // the rounds on the rows that stayed in registers
+#pragma unroll
+      for (int i = 0; i < NKEEP; ++i)
+        if (i < n) body(vkeep[i], i);
+    };
+    // The other full-plan kernels walk rows 0 .. n-1 in one straight-line instance per n <= KRING: with no branch between
+    // a load and its use the compiler counts the outstanding loads exactly (s_waitcnt vmcnt(2*MAXM) in the steady state
+    // instead of vmcnt(0)), so the requests are exact as well — no clamping, a guarded refill, nothing left in flight.
+    auto cases_request = [&](T (&buf)[NBUF][NVEC], int n) {
+#pragma unroll
+      for (int i = 0; i < NBUF; ++i)
+        if (i + NKEEP < n) load_vec(buf[i], vrow(i + NKEEP));
+    };
+    auto ring_cases = [&](T (&buf)[NBUF][NVEC], int n, auto&& body, auto&& pre, auto&& post) {
+      auto rounds = [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+          if constexpr (NKEEP > 0) {
+            if (i < NKEEP) {
+              body(vkeep[i < NKEEP ? i : 0], i);
+              continue;
+            }
+          }
+          pre(K - 1 - i < NBUF - 1 ? K - 1 - i : NBUF - 1);
+          body(buf[(i - NKEEP) % NBUF], i);
+          if (i + NBUF < K) load_vec(buf[(i - NKEEP) % NBUF], vrow(i + NBUF));
+          post();
+        }
+      };
+#define CGM_KCASE(n) \
+  case n:            \
+    rounds(std::integral_constant<int, n>{}); \
+    break;
+      switch (n) {
+        CGM_KCASE(1) CGM_KCASE(2) CGM_KCASE(3) CGM_KCASE(4) CGM_KCASE(5) CGM_KCASE(6)
+        CGM_KCASE(7) CGM_KCASE(8) CGM_KCASE(9) CGM_KCASE(10) CGM_KCASE(11) CGM_KCASE(12)
+        default: break;
+      }
+#undef CGM_KCASE
+    };
+    static_assert(KRING == 12, "ring_cases has one case per basis length");
+    auto no_stamp = [](auto...) {};
     // Diagnostic build: the Gram-Schmidt stamp split in three — 28 closes an explicit wait for the ring row a round is
     // about to use (the `younger` rows requested after it stay in flight, as in the product build), 29 the ring round
     // itself (arithmetic, instruction fetch, refill request), 7 keeps the register rounds and the norm.
@@ -2433,16 +2526,8 @@ struct WgCtx {
       auto request_rows = [&]() {
         if (preload && active) {
           __builtin_amdgcn_s_waitcnt(0x0F70);
-          if constexpr (COMPACT) {
-            if (k > NKEEP) {  // (all NBUF buffers or none: buffers past the last needed row re-read it)
-#pragma unroll
-              for (int i = 0; i < NBUF; ++i) load_vec(vbuf[i], vrow(i + NKEEP < k ? i + NKEEP : k - 1));
-            }
-          } else {
-#pragma unroll
-          for (int i = 0; i < NBUF; ++i)
-            if (i + NKEEP < k) load_vec(vbuf[i], vrow(i + NKEEP));
-          }
+          if constexpr (COMPACT) ring_request(vbuf, NKEEP, k);
+          else cases_request(vbuf, k);
         }
       };
       if (NWT == 0 && tid >= 64) request_rows();
@@ -2455,22 +2540,16 @@ struct WgCtx {
       };
       if constexpr (NWT != 0) {
         CGM_STAMP(*this, 3);
-        // (twelve-case form of the rounds: the basis rows are requested between the Newton iterations and the costate
-        // scans: early enough to arrive behind the scans, late enough that their registers are not live across the
-        // iterations, where the register file is fullest — requested before the sweep they sit in AGPRs and every use in
-        // the rounds below is a copy)
+        request_rows();
         if constexpr (NWT == 2) {
-          request_rows();  // (a light sweep: the rows may be in flight across it)
+          // (a light sweep: the rows may be in flight across it)
           row_affine_sweep<F_AX>(S.xh, dtau_h, S.W + inst * P.Lp, S.W, active);
         } else {
-          if constexpr (COMPACT) {
-            // (compact rounds: the ring sits in AGPRs whichever way — requested here, a whole sweep ahead, the first NBUF
-            // rows have arrived when their rounds come: 86.5 vs 87.6 us per tick, profiles/r07_gs_ab.json)
-            request_rows();
-            row_newton_sweep<F_AX>(dtau_h, vcur, w, active, [] {});  // :48  w <- A v_k, registers to registers
-          } else {
-            row_newton_sweep<F_AX>(dtau_h, vcur, w, active, request_rows);
-          }
+          static_assert(COMPACT, "the row-Newton sweep goes with the clamped ring");
+          // (the ring sits in AGPRs whichever way — requested here, a whole sweep ahead, the first NBUF rows have arrived
+          // when their rounds come: 86.5 vs 87.6 us per tick against a request between the Newton iterations and the
+          // costate scans, profiles/r07_gs_ab.json)
+          row_newton_sweep<F_AX>(dtau_h, vcur, w, active);  // :48  w <- A v_k, registers to registers
         }
         CGM_STAMP(*this, 6);
       } else {
@@ -2489,101 +2568,24 @@ struct WgCtx {
         }
         T* Hk = Hi + hoff(k);
         // modified Gram-Schmidt, gmres.hpp:52-58, in order; v_k itself is still in registers
-        auto mgs_round = [&](const T* vi, int i) {
-          T pa = 0, pb = 0;  // two partial sums: the fp64 FMA chain is latency-bound (8 cycles/op dependent)
-#pragma unroll
-          for (int m = 0; m < NVEC; m += 2) {
-            pa += vi[m] * w[m];
-            if (m + 1 < NVEC) pb += vi[m + 1] * w[m + 1];
-          }
-          const T hik = row16_sum(pa + pb);
-#pragma unroll
-          for (int m = 0; m < NVEC; ++m) w[m] = w[m] - vi[m] * hik;
-          if (r == 0) Hk[i] = hik;
-        };
+        auto round = [&](const T* vi, int i) { mgs_round(w, Hk, vi, i); };
         if (preload) {
           if constexpr (COMPACT) {
-#pragma unroll
-            for (int i = 0; i < NKEEP; ++i)
-              if (i < k) mgs_round(vkeep[i], i);
-            if (k > NKEEP) {
-              int i = NKEEP;
-              for (; i + NBUF <= k; i += NBUF) {
-#pragma unroll
-                for (int d = 0; d < NBUF; ++d) {
-                  stamp_row_wait(NBUF - 1);
-                  mgs_round(vbuf[d], i + d);
-                  const int nxt = i + d + NBUF;
-                  load_vec(vbuf[d], vrow(nxt < k ? nxt : k - 1));
-                  stamp_ring_round();
-                }
-              }
-#pragma unroll
-              for (int d = 0; d < NBUF - 1; ++d)
-                if (i + d < k) {
-                  stamp_row_wait(NBUF - 1 - d);
-                  mgs_round(vbuf[d], i + d);
-                  stamp_ring_round();
-                }
-            }
+            keep_rows(k, round);
+            if (k > NKEEP) ring_walk<false>(vbuf, NKEEP, k, round, stamp_row_wait, stamp_ring_round);
           } else {
-          // One straight-line instance per k: with no branch between a load and its use the compiler counts the
-          // outstanding loads exactly (s_waitcnt vmcnt(2*MAXM) in the steady state instead of vmcnt(0)).
-          auto rounds = [&](auto kc) {
-            constexpr int K = decltype(kc)::value;
-#pragma unroll
-            for (int i = 0; i < K; ++i) {
-              if constexpr (NKEEP > 0) {
-                if (i < NKEEP) {
-                  mgs_round(vkeep[i < NKEEP ? i : 0], i);
-                  continue;
-                }
-              }
-              stamp_row_wait(K - 1 - i < NBUF - 1 ? K - 1 - i : NBUF - 1);
-              mgs_round(vbuf[(i - NKEEP) % NBUF], i);
-              if (i + NBUF < K) load_vec(vbuf[(i - NKEEP) % NBUF], vrow(i + NBUF));
-              stamp_ring_round();
-            }
-          };
-          switch (k) {
-            CGM_KCASES(rounds)
-            default: break;
-          }
+            ring_cases(vbuf, k, round, stamp_row_wait, stamp_ring_round);
           }
         } else {
           // (register-starved lean kernels: v_k is streamed back from its row like the older ones instead of being
           // held in registers through the whole sweep; the row was written by this same thread)
-          // The next row is requested UNCONDITIONALLY (the last trip re-reads its own row): a guard would be a branch
-          // between a load and its use, and the compiler then waits with vmcnt(0) — i.e. also for the row it has just
-          // requested, and nothing overlaps.
-          // SDEPTH row buffers with STATIC indices (no rotation by register moves: 20 v_mov per round, and a move would
-          // wait for the newest request): the main loop does SDEPTH rounds per trip and refills each buffer right after
-          // its round (row index clamped: the last trips re-read the last row), the remaining < SDEPTH rounds find
-          // their rows already requested.
           T vq[SDEPTH][NVEC];
           const int kk = VK_IN_REGS ? k : k + 1;
-          if (kk > 0) {
-#pragma unroll
-            for (int d = 0; d < SDEPTH; ++d) load_vec(vq[d], vrow(d < kk ? d : kk - 1));
-          }
-          int i = 0;
-          for (; i + SDEPTH <= kk; i += SDEPTH) {
-#pragma unroll
-            for (int d = 0; d < SDEPTH; ++d) {
-              // (keeps the requests TOGETHER and ahead of the arithmetic: under register pressure the scheduler otherwise
-              // sinks every load next to its use — one exposed round trip per element)
-              __builtin_amdgcn_sched_barrier(0);
-              mgs_round(vq[d], i + d);
-              const int nxt = i + d + SDEPTH;
-              load_vec(vq[d], vrow(nxt < kk ? nxt : kk - 1));
-            }
-          }
-#pragma unroll
-          for (int d = 0; d < SDEPTH - 1; ++d)
-            if (i + d < kk) mgs_round(vq[d], i + d);
+          ring_request(vq, 0, kk);
+          ring_walk<true>(vq, 0, kk, round, no_stamp, no_stamp);
           drain_stream();
         }
-        if constexpr (VK_IN_REGS) mgs_round(vcur, k);
+        if constexpr (VK_IN_REGS) round(vcur, k);
         T na = 0, nb = 0;
 #pragma unroll
         for (int m = 0; m < NVEC; m += 2) {
@@ -2688,16 +2690,8 @@ struct WgCtx {
     // the first basis rows of the x update are requested before the (serial) back substitution
     T vbx[NBUF][NVEC];
     if (preload && valid && reason <= 1) {
-      if constexpr (COMPACT) {
-        if (ks > NKEEP) {
-#pragma unroll
-          for (int j = 0; j < NBUF; ++j) load_vec(vbx[j], vrow(j + NKEEP < ks ? j + NKEEP : ks - 1));
-        }
-      } else {
-#pragma unroll
-      for (int j = 0; j < NBUF; ++j)
-        if (j + NKEEP < ks) load_vec(vbx[j], vrow(j + NKEEP));
-      }
+      if constexpr (COMPACT) ring_request(vbx, NKEEP, ks);
+      else cases_request(vbx, ks);
     }
     if (valid && reason <= 1) {
       // back substitution (gmres.hpp:100-107), column-oriented over the lanes of the row: lane j owns e_j; step i
@@ -2750,80 +2744,21 @@ struct WgCtx {
       T acc[NVEC];
 #pragma unroll
       for (int m = 0; m < NVEC; ++m) acc[m] = T(0.0);
-      if (preload) {
-        if constexpr (COMPACT) {  // the Gram-Schmidt rounds' loop: keep rows, NBUF ring rounds per trip, tail, drain
-          auto axpy = [&](const T* vj, int j) {
-            const T yj = rhoi[j];
-#pragma unroll
-            for (int m = 0; m < NVEC; ++m) acc[m] += vj[m] * yj;
-          };
-#pragma unroll
-          for (int j = 0; j < NKEEP; ++j)
-            if (j < ks) axpy(vkeep[j], j);
+      auto term = [&](const T* vj, int j) { axpy(acc, rhoi, vj, j); };
+      if (preload) {  // the Gram-Schmidt rounds' walk, on the rows requested before the back substitution
+        if constexpr (COMPACT) {
+          keep_rows(ks, term);
           if (ks > NKEEP) {
-            int j = NKEEP;
-            for (; j + NBUF <= ks; j += NBUF) {
-#pragma unroll
-              for (int d = 0; d < NBUF; ++d) {
-                axpy(vbx[d], j + d);
-                const int nxt = j + d + NBUF;
-                load_vec(vbx[d], vrow(nxt < ks ? nxt : ks - 1));
-              }
-            }
-#pragma unroll
-            for (int d = 0; d < NBUF - 1; ++d)
-              if (j + d < ks) axpy(vbx[d], j + d);
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // the look-ahead nobody consumes (see the Gram-Schmidt rounds)
+            ring_walk<false>(vbx, NKEEP, ks, term, no_stamp, no_stamp);
+            drain_stream();
           }
-        } else {  // same register ring as the Gram-Schmidt rounds
-        auto& vbuf = vbx;
-        auto rounds = [&](auto kc) {
-          constexpr int K = decltype(kc)::value;
-#pragma unroll
-          for (int j = 0; j < K; ++j) {
-            const T yj = rhoi[j];
-            if constexpr (NKEEP > 0) {
-              if (j < NKEEP) {
-#pragma unroll
-                for (int m = 0; m < NVEC; ++m) acc[m] += vkeep[j < NKEEP ? j : 0][m] * yj;
-                continue;
-              }
-            }
-#pragma unroll
-            for (int m = 0; m < NVEC; ++m) acc[m] += vbuf[(j - NKEEP) % NBUF][m] * yj;
-            if (j + NBUF < K) load_vec(vbuf[(j - NKEEP) % NBUF], vrow(j + NBUF));
-          }
-        };
-        switch (ks) {
-          CGM_KCASES(rounds)
-          default: break;
-        }
+        } else {
+          ring_cases(vbx, ks, term, no_stamp, no_stamp);
         }
       } else {
-        // streaming form, SDEPTH rows in flight (see the Gram-Schmidt loop)
         T vq[SDEPTH][NVEC];
-        if (ks > 0) {
-#pragma unroll
-          for (int d = 0; d < SDEPTH; ++d) load_vec(vq[d], vrow(d < ks ? d : ks - 1));
-        }
-        auto axpy = [&](const T* vj, int j) {
-          const T yj = rhoi[j];
-#pragma unroll
-          for (int m = 0; m < NVEC; ++m) acc[m] += vj[m] * yj;
-        };
-        int j = 0;
-        for (; j + SDEPTH <= ks; j += SDEPTH) {
-#pragma unroll
-          for (int d = 0; d < SDEPTH; ++d) {
-            __builtin_amdgcn_sched_barrier(0);
-            axpy(vq[d], j + d);
-            const int nxt = j + d + SDEPTH;
-            load_vec(vq[d], vrow(nxt < ks ? nxt : ks - 1));
-          }
-        }
-#pragma unroll
-        for (int d = 0; d < SDEPTH - 1; ++d)
-          if (j + d < ks) axpy(vq[d], j + d);
+        ring_request(vq, 0, ks);
+        ring_walk<true>(vq, 0, ks, term, no_stamp, no_stamp);
         drain_stream();
       }
 #pragma unroll

@@ -32,11 +32,11 @@ def _batch(B, dv, km, tol):
     return c
 
 
-def _oracle_free_run(orc, dv, km, tol, x0, u0, p, ticks):
+def _oracle_free_run(orc, dv, km, tol, x0, u0, p, ticks, model=0):
     """x, u after `ticks` closed-loop ticks and the Arnoldi counts / exit reasons of every tick, per instance."""
     xs, us, counts, reasons = [], [], [], []
     for i in range(len(x0)):
-        r = orc.Controller(0, dv, km, tol)
+        r = orc.Controller(model, dv, km, tol)
         orc.start_controller(r, x0[i], u0[i], p[i])
         x, ks, rs = x0[i].copy(), [], []
         for _ in range(ticks):
