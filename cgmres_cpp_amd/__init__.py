@@ -28,6 +28,7 @@ TICKS_PER_LAUNCH = 10  # CGMRES_HIP_TICKS_PER_LAUNCH: closed_loop_device fuses t
 SYMBOLS = [
     "cgmres_hip_model_info", "cgmres_hip_default_config", "cgmres_hip_model_probe", "cgmres_hip_register_model",
     "cgmres_hip_selftest_sincos", "cgmres_hip_register_operator", "cgmres_hip_operator_info", "cgmres_hip_gmres_user",
+    "cgmres_hip_operator_plan",
     "cgmres_hip_last_error",
     "cgmres_hip_device_count", "cgmres_hip_create", "cgmres_hip_destroy", "cgmres_hip_get_config", "cgmres_hip_variant_name",
     "cgmres_hip_set_ptau", "cgmres_hip_set_ptau_repeat", "cgmres_hip_init_u0", "cgmres_hip_init_u0_newton",
@@ -86,6 +87,7 @@ def load():
                                                C.POINTER(C.c_double)]
     lib.cgmres_hip_register_operator.argtypes = [C.c_char_p, C.POINTER(i32)]
     lib.cgmres_hip_operator_info.argtypes = [i32, C.POINTER(i32)]
+    lib.cgmres_hip_operator_plan.argtypes = [i32, i32, C.POINTER(i32)]
     lib.cgmres_hip_gmres_user.argtypes = [i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp]
     lib.cgmres_hip_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
     lib.cgmres_hip_destroy.argtypes = [vp]
@@ -185,6 +187,14 @@ def gmres_user(op_id, x0, b, k_max, tol, params=None, device=0):
     _check(load().cgmres_hip_gmres_user(op_id, device, B, int(k_max), float(tol), pp.ctypes.data if npar else None,
                                         x.ctypes.data, bb.ctypes.data, n_ax.ctypes.data, why.ctypes.data))
     return x, n_ax, why
+
+
+def operator_plan(op_id, k_max):
+    """cgmres_hip_operator_plan: (form, mapping) of a k_max solve with a registered operator — form "serial" (Op::Ax on
+    one lane) | "row" (Op::Ax_row on all lanes), mapping "lane" | "wave" (one lane / one wavefront per system).  No GPU."""
+    out = (C.c_int32 * 2)()
+    _check(load().cgmres_hip_operator_plan(op_id, int(k_max), out))
+    return ("serial", "row")[out[0]], ("lane", "wave")[out[1]]
 
 
 class DeviceBuffer:

@@ -15,6 +15,7 @@
 
 #include "ctx_common.hip.h"
 #include "factory.hip.h"
+#include "gmres_plan.hip.h"
 #include "util_kernels.hip.h"
 
 namespace {
@@ -51,6 +52,7 @@ struct OpPlugin {
   int32_t len, n_params;
   int (*solve)(int32_t, int32_t, int32_t, double, const double*, double*, const double*, int32_t*, int32_t*);
   const char* (*last_error)(void);
+  void (*plan)(int32_t, int32_t*);  // optional symbol: null in a plugin built before the row form existed (serial form)
 };
 std::deque<OpPlugin>& op_plugins() {
   static std::deque<OpPlugin> v;
@@ -271,6 +273,7 @@ int cgmres_hip_register_operator(const char* plugin_path, int32_t* op_id) {
   pl.dl = dl, pl.path = plugin_path;
   pl.solve = reinterpret_cast<decltype(pl.solve)>(dlsym(dl, "cgmres_hip_opplugin_solve"));
   pl.last_error = reinterpret_cast<decltype(pl.last_error)>(dlsym(dl, "cgmres_hip_opplugin_last_error"));
+  pl.plan = reinterpret_cast<decltype(pl.plan)>(dlsym(dl, "cgmres_hip_opplugin_plan"));
   if (!abi || !info || !pl.solve || !pl.last_error) {
     dlclose(dl);
     return fail(CGMRES_HIP_EINVAL, "register_operator: %s is not a cgmres_hip operator plugin", plugin_path);
@@ -296,6 +299,20 @@ int cgmres_hip_operator_info(int32_t op_id, int32_t dims[2]) {
   const OpPlugin* pl = find_op(op_id);
   if (!pl || !dims) return fail(CGMRES_HIP_EINVAL, "operator_info: unknown operator %d", op_id);
   dims[0] = pl->len, dims[1] = pl->n_params;
+  return 0;
+}
+
+int cgmres_hip_operator_plan(int32_t op_id, int32_t k_max, int32_t out[2]) {
+  const OpPlugin* pl = find_op(op_id);
+  if (!pl || !out) return fail(CGMRES_HIP_EINVAL, "operator_plan: unknown operator %d", op_id);
+  if (!cgm::gmres_sizes_ok(pl->len, k_max))
+    return fail(CGMRES_HIP_EINVAL, "operator_plan: k_max %d is no solve of a len %d operator", k_max, pl->len);
+  if (pl->plan) {
+    pl->plan(k_max, out);  // the function the plugin's own solve launches by
+  } else {
+    const cgm::GmresPlan p = cgm::gmres_plan(pl->len, k_max, false);
+    out[0] = p.form, out[1] = p.mapping;
+  }
   return 0;
 }
 

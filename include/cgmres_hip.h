@@ -137,12 +137,21 @@ int cgmres_hip_model_probe(int32_t model_id, int32_t device, const double* x, co
 int cgmres_hip_register_model(const char* plugin_path, int32_t* model_id);
 /* ---- stand-alone Gmres with a caller-supplied operator: class Gmres, reference include/gmres.hpp:8-129 ------------ */
 /* Registers a device OPERATOR: `plugin_path` is a shared object generated by cgmres_cpp_amd/plugin.py
- * (build_operator) from a header with `struct Op { static constexpr int len, n_params; static void Ax(double* Ax,
- * const double* x, const double* params); }` — the device build of a subclass's `Ax_func` (gmres.hpp:26).
- * *op_id receives an id for cgmres_hip_gmres_user; the same path twice returns the same id. */
+ * (build_operator) from a header with `struct Op { static constexpr int len, n_params; ... }` — the device build of a
+ * subclass's `Ax_func` (gmres.hpp:26) — whose product comes in one of two forms (or both; detected at compile time):
+ *   static double Ax_row(int i, const double* x, const double* params);   the ROW form: element i of A x.  The rows of
+ *       a product run on all 64 lanes of the wavefront that owns the system.  Write this one whenever a row can be
+ *       computed on its own (stencils, sparse and dense rows, anything without a recurrence across rows).
+ *   static void Ax(double* Ax, const double* x, const double* params);    the SERIAL form: the whole vector, like
+ *       Ax_func.  One lane runs it while 63 wait; for operators that cannot be split by rows.
+ * With both defined the device uses Ax_row (Ax then serves the host subclass).  *op_id receives an id for cgmres_hip_gmres_user; the same path twice returns the same id. */
 int cgmres_hip_register_operator(const char* plugin_path, int32_t* op_id);
 /* dims[0] = len, dims[1] = n_params of a registered operator */
 int cgmres_hip_operator_info(int32_t op_id, int32_t dims[2]);
+/* out[0] = 0 serial Ax / 1 Ax_row; out[1] = 0 one lane per system / 1 one wavefront per system, for this k_max.
+ * Pure host arithmetic: needs no GPU.  It is the function cgmres_hip_gmres_user launches by.  A plugin built before the
+ * row form existed reports the serial form. */
+int cgmres_hip_operator_plan(int32_t op_id, int32_t k_max, int32_t out[2]);
 /* Gmres::gmres(x, b) (gmres.hpp:28-112) for `batch` independent systems A(params_i) x_i = b_i, all with the same
  * k_max and tol, on the GPU: x [batch][len] in/out (the warm start, :33), b [batch][len], params [batch][n_params]
  * (NULL when n_params = 0); n_ax / reason [batch] as in cgmres_hip_get_status (NULL skips).  Host pointers; blocks. */

@@ -10,7 +10,12 @@
 // a shared object generated from the header that holds the operator (`struct Op { static constexpr int len, n_params;
 // static void Ax(double* Ax, const double* x, const double* params); }` — the same function its host Ax_func calls) by
 // `python -m cgmres_cpp_amd.plugin --operator <header> --cls Op`; gmres(x, b) then is cgmres_hip_gmres_user for a batch of
-// one.  There is NO host implementation behind gmres(): without a registered operator the call ends the program with a
+// one.  The operator comes in two forms, detected at compile time (nothing changes in this class or in the build):
+//   static void Ax(double* Ax, const double* x, const double* params);    SERIAL: the whole vector, like Ax_func — one
+//                                                                         lane of the system's wavefront runs it
+//   static double Ax_row(int i, const double* x, const double* params);   ROW: element i of A x — all 64 lanes run rows
+// Write Ax_row whenever a row can be computed on its own (then Ax, if the host Ax_func wants one, is a loop over the
+// rows); with both present the device uses Ax_row.  cgmres_hip_operator_plan tells which form and mapping a solve takes.  There is NO host implementation behind gmres(): without a registered operator the call ends the program with a
 // message (the reference's own failure convention, DEBUG_MODE's exit(-1)) — never a silent CPU fallback.
 // Thousands of systems at once: cgmres_hip_gmres_user directly (include/cgmres_hip.h).
 #pragma once

@@ -1,0 +1,328 @@
+"""The ROW form of the stand-alone Gmres's operator contract (csrc/user_operator.hip.h: `static double Ax_row(int i,
+const double* x, const double* params)`, element i of A x): the rows of a product run on all 64 lanes of the wavefront
+that owns a system instead of one serial `Ax` on lane 0.  tests/user_models/gmres_row_ops.hpp holds row-form twins of the
+operators of gmres_ops.hpp — bit-identical on the host (test_operator_twins_agree), which entitles them to the reference
+fixtures tests/golden/user_gmres_*.txt of tests/test_user_gmres.py.  cgmres_hip_operator_plan tells every test which
+form and which mapping (one wavefront / one lane per system) the solve it checks takes.
+
+Where this file departs from the letter of the issue that asked for it, because the issue contradicts itself there:
+  * len 840 at k_max = 20.  The issue wants the row form to drop the `vout` row from GmresWaveLds::count ("flips one
+    len-row later than the serial form") AND wants ConvDiffRowOpN<840> at k_max = 20 to report "lane".  22 rows of 840
+    doubles + 2368 B are 150208 B <= 153600 B: with the row dropped that solve fits a wavefront.  The plan tests assert
+    what the count says (serial: lane from k_max = 20, row: lane from k_max = 21); the lane-path test runs the serial
+    form at k_max = 20 and 21 and the row form at k_max = 21 on the lane kernel (and the row form at k_max = 20 on the
+    wave kernel), all against reference records — the fixture holds both k_max.
+  * len 1 with 30 iterations at tol = 1e-6.  At len 1 the first Arnoldi vector is 0 after Gram-Schmidt up to the rounding
+    of v0 = r / |r|, so the reference's loop ends at k = 0 — "Breakdown" (gmres.hpp:63) or, where that norm stays above
+    DBL_EPSILON, convergence (:93) with an empty triangular solve — and x is untouched either way: no residual bound can
+    hold.  The test asserts that outcome instead; the residual bound stands at len 64 and 65.  Instance 0 of the
+    scenario is 0 x = 0 from x0 = 0 at len 1 (tol = 0 divides by its zero residual): these cases use instances 1..6."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import cgmres_cpp_amd as cg
+from cgmres_cpp_amd import plugin
+from test_user_gmres import CASES, N_INST, TOLS, fixture, scenario
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+UM = os.path.join(ROOT, "tests", "user_models")
+OPS = os.path.join(UM, "gmres_ops.hpp")
+ROW_OPS = os.path.join(UM, "gmres_row_ops.hpp")
+ROW_CLS = {"spd": "SpdTridiagRowOp", "convdiff": "ConvDiffRowOp", "convdiff150": "ConvDiffRowOp150",
+           "convdiff300": "ConvDiffRowOp300"}
+FIXTURE_840 = os.path.join(ROOT, "tests", "golden", "user_gmres_convdiff840.txt")
+LDS_LIMIT = 150 * 1024  # kGmresWaveLdsLimit
+
+needs_hipcc = pytest.mark.skipif(not os.path.exists(plugin._build.HIPCC), reason="hipcc not available")
+
+
+def row_op(name):
+    """id of the row-form twin of CASES[name] / of the stencil at len = int(name) (built once: __graft_entry__.build)"""
+    cls = ROW_CLS[name] if name in ROW_CLS else f"ConvDiffRowOp{name}"
+    tag = name if name in ROW_CLS else f"convdiff{name}"
+    return plugin.register_operator(plugin.build_operator(ROW_OPS, cls, name=f"{tag}_row"))
+
+
+def serial_op(n):
+    """id of the serial stencil of gmres_ops.hpp at len = n"""
+    return plugin.register_operator(plugin.build_operator(OPS, f"ConvDiffOpN<{n}>", name=f"convdiff{n}_serial"))
+
+
+def wave_lds_count(L, kmax, row):
+    """GmresWaveLds::count, written down from the layout: operand row (+ result row of a serial operator), k_max + 1
+    basis rows, compact Hessenberg (even pitch), k_max + 2 residual entries, 3 k_max reflector scalars, 2 spare."""
+    pitch_h = ((kmax * (kmax + 1)) // 2 + 2) & ~1
+    return (kmax + 1 + (1 if row else 2)) * L + pitch_h + (kmax + 2) + 3 * kmax + 2
+
+
+def stencil(L, i):
+    """(params, b, x0) of instance i at length L: the scenario of test_user_gmres.py at any length"""
+    e = np.arange(L)
+    return np.array([0.4 + 0.07 * i, 0.35 - 0.02 * i]), np.sin(0.3 * e + 0.5 * i) + 0.1 * e, 0.01 * (e - i)
+
+
+def dense_stencil(L, p):
+    A = np.zeros((L, L))
+    for i in range(L):
+        A[i, i] += 2.0 + p[0] + 0.01 * i
+        if i > 0:
+            A[i, i - 1] -= 1.0 + p[1]
+        if i + 1 < L:
+            A[i, i + 1] -= 1.0 - p[1]
+        A[i, (i * 7 + 3) % L] += 0.05
+    return A
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------------------
+@needs_hipcc
+def test_row_only_header_builds_registers_and_plans():
+    """A struct with ONLY Ax_row: the glue must not name Op::Ax.  (Fails to compile before the row form existed.)"""
+    so = plugin.build_operator(ROW_OPS, "ConvDiffRowOp", name="convdiff_row")
+    syms = subprocess.run(["nm", "-D", "--defined-only", so], check=True, capture_output=True, text=True).stdout
+    for s in ("cgmres_hip_opplugin_abi", "cgmres_hip_opplugin_info", "cgmres_hip_opplugin_solve",
+              "cgmres_hip_opplugin_last_error", "cgmres_hip_opplugin_plan"):
+        assert s in syms
+    for name in ("spd", "convdiff", "convdiff150", "convdiff300"):  # (150 / 300: both forms defined -> the row form)
+        oid = row_op(name)
+        d = (cg.C.c_int32 * 2)()
+        cg._check(cg.load().cgmres_hip_operator_info(oid, d))
+        assert (d[0], d[1]) == CASES[name][1:3]
+        for kmax in CASES[name][3]:
+            assert cg.operator_plan(oid, kmax) == ("row", "wave"), (name, kmax)
+    with pytest.raises(cg.CgmresHipError):
+        cg.operator_plan(10 ** 6, 5)
+    with pytest.raises(cg.CgmresHipError):
+        cg.operator_plan(row_op("convdiff"), 0)
+
+
+@needs_hipcc
+def test_serial_operators_keep_the_serial_form():
+    for name, (cls, L, npar, kmaxs) in CASES.items():
+        oid = plugin.register_operator(plugin.build_operator(OPS, cls, name=name))
+        for kmax in kmaxs:
+            assert cg.operator_plan(oid, kmax) == ("serial", "wave"), (name, kmax)
+
+
+@needs_hipcc
+def test_mapping_flips_where_the_lds_count_says():
+    """len 840: 23 rows of 840 doubles (154560 B) exceed the 150 KB of a wavefront's plan, 22 rows + the small arrays
+    (150208 B) do not — the serial form leaves the wave mapping at k_max = 20, the row form (no `vout` row) one len-row
+    later, at k_max = 21.  len 300: the flip of both forms deep inside the valid k_max range."""
+    for L in (840, 300):
+        if L == 840:
+            ids = {False: serial_op(840), True: row_op("840")}
+        else:
+            ids = {False: plugin.register_operator(plugin.build_operator(OPS, "ConvDiffOp300", name="convdiff300")),
+                   True: row_op("convdiff300")}
+        kmax_valid = [k for k in range(1, 80) if L * (k + 1) < 65536]
+        first_lane = {}
+        for row in (False, True):
+            got = [cg.operator_plan(ids[row], k) for k in kmax_valid]
+            assert all(g[0] == ("row" if row else "serial") for g in got)
+            want = ["wave" if wave_lds_count(L, k, row) * 8 <= LDS_LIMIT else "lane" for k in kmax_valid]
+            assert [g[1] for g in got] == want, (L, row)
+            first_lane[row] = kmax_valid[want.index("lane")]
+            assert want == ["wave"] * want.index("lane") + ["lane"] * (len(want) - want.index("lane"))  # one flip
+            assert all(wave_lds_count(L, k, True) == wave_lds_count(L, k, False) - L for k in kmax_valid)
+        if L == 840:
+            assert first_lane == {False: 20, True: 21}
+            assert 23 * 840 * 8 > LDS_LIMIT and 840 * 21 < 65536
+            assert cg.operator_plan(ids[False], 20) == ("serial", "lane")
+            assert cg.operator_plan(ids[True], 20) == ("row", "wave") and cg.operator_plan(ids[True], 21) == ("row", "lane")
+        else:
+            assert first_lane[True] >= first_lane[False]
+    with pytest.raises(cg.CgmresHipError):  # 840 * 79 >= 65536: no solve, no plan
+        cg.operator_plan(row_op("840"), 78)
+
+
+def test_a_plugin_without_the_plan_symbol_is_the_serial_form(tmp_path):
+    """A plugin built before the row form existed has no cgmres_hip_opplugin_plan: it still registers (the ABI version
+    did not move) and its plan is the serial form with the serial LDS count (len 840: lane from k_max = 20)."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    so = tmp_path / "libcgmres_op_old.so"
+    subprocess.run(["g++", "-shared", "-fPIC", "-std=c++17", f"-I{ROOT}/include",
+                    os.path.join(UM, "old_operator_plugin_stub.cpp"), "-o", str(so)], check=True)
+    syms = subprocess.run(["nm", "-D", "--defined-only", str(so)], check=True, capture_output=True, text=True).stdout
+    assert "cgmres_hip_opplugin_solve" in syms and "cgmres_hip_opplugin_plan" not in syms
+    oid = plugin.register_operator(str(so))
+    assert cg.operator_plan(oid, 19) == ("serial", "wave") and cg.operator_plan(oid, 20) == ("serial", "lane")
+    assert cg.operator_plan(oid, 5) == ("serial", "wave")
+
+
+def test_operator_twins_agree(tmp_path):
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = tmp_path / "twins"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", f"-I{UM}", os.path.join(UM, "gmres_twins_main.cpp"),
+                    "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout
+    lines = r.stdout.strip().split("\n")
+    assert len(lines) == 9 and all(l.endswith("mismatches 0") for l in lines), r.stdout
+
+
+@needs_hipcc
+def test_a_struct_with_neither_form_does_not_build():
+    with pytest.raises(RuntimeError) as ei:
+        plugin.build_operator(ROW_OPS, "NeitherFormOp", name="neither_form", force=True)
+    msg = str(ei.value)
+    assert "static assertion failed" in msg or "static_assert" in msg
+    assert "static void Ax(double* Ax, const double* x, const double* params)" in msg
+    assert "static double Ax_row(int i, const double* x, const double* params)" in msg
+
+
+@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="/root/reference not mounted (GPU box)")
+def test_lane_fixture_is_what_the_reference_solver_prints(tmp_path):
+    """tests/user_models/gmres_lane_main.cpp against the reference's include/: its output is the committed fixture, and
+    every h(k+1,k) of those runs is far above rounding (> 1e-6; they are O(1)) — 20 (21) Arnoldi steps on any build."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = tmp_path / "gmres_lane_main"
+    subprocess.run(["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-I/root/reference/include", f"-I{UM}",
+                    os.path.join(UM, "gmres_lane_main.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    assert out == open(FIXTURE_840).read()
+    hs = subprocess.run([str(exe), "hsub"], check=True, capture_output=True, text=True).stdout.strip().split("\n")
+    assert len(hs) == 4
+    for line in hs:
+        v = [float(t) for t in line.split()]
+        assert len(v) == 2 + int(v[1]) and min(v[2:]) > 1e-6, line
+
+
+def fixture_840():
+    rows = np.loadtxt(FIXTURE_840)
+    assert rows.shape == (4, 3 + 840) and np.array_equal(rows[:, 0], [0, 1, 0, 1]) and np.array_equal(rows[:, 1], [20, 20, 21, 21])
+    return rows
+
+
+def test_lane_fixture_is_a_partial_solve():
+    """20 iterations on 840 unknowns: the residual has dropped but is nowhere near the rounding floor (numpy, no GPU)."""
+    for r in fixture_840():
+        p, b, x0 = stencil(840, int(r[0]))
+        A = dense_stencil(840, p)
+        res, res0 = np.linalg.norm(A @ r[3:] - b), np.linalg.norm(A @ x0 - b)
+        assert 1e-9 * res0 < res < res0
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(CASES))
+def test_row_operator_vs_the_reference(name):
+    """The records of the UNMODIFIED reference solver, as in test_device_gmres_with_a_user_operator_vs_the_reference: same
+    scenarios, (k_max, tol) cases, bound and exit bookkeeping — with the operator's rows on all lanes.  len 24 / 40:
+    fewer elements than lanes; 150 = 2*64 + 22, 300 = 4*64 + 44: a ragged last element group, both-forms structs."""
+    cls, L, npar, kmaxs = CASES[name]
+    oid = row_op(name)
+    rows = fixture(name)
+    for c, (kmax, tol) in enumerate(zip(kmaxs, TOLS)):
+        assert cg.operator_plan(oid, kmax) == ("row", "wave")
+        n = N_INST[name]
+        P, Bv, X0 = zip(*[scenario(name, i) for i in range(n)])
+        x, n_ax, why = cg.gmres_user(oid, np.array(X0), np.array(Bv), kmax, tol, np.array(P))
+        ref = rows[n * c:n * c + n]
+        assert np.array_equal(ref[:, 0], np.arange(n)) and np.all(ref[:, 1] == kmax)
+        scale = np.max(np.abs(ref[:, 3:]))
+        err = np.max(np.abs(x - ref[:, 3:]))
+        print(f"{name} k_max {kmax} tol {tol}: |dx|inf {err:.3e} (bound {1e-9 * scale:.3e})")
+        assert err <= 1e-9 * scale, (name, kmax, tol, err)
+        assert np.all(n_ax <= kmax) and np.all(n_ax >= 1)
+        if tol == 0.0 and kmax < L:
+            assert np.all(n_ax == kmax) and np.all(why == cg.EXIT_NATURAL)
+        assert np.all((why == cg.EXIT_NATURAL) | (why == cg.EXIT_CONVERGED) | (why == cg.EXIT_BREAKDOWN))
+        if tol > 0 and kmax >= L:
+            assert np.all(why != cg.EXIT_NATURAL)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("L", [1, 64, 65])
+def test_lane_boundary_lengths_row_vs_serial(L):
+    """A single element, exactly one element per lane, one lane with two: the row form against the serial form of the
+    same stencil on the device (which the reference pins at the other lengths).  Same kernel, operator values equal
+    element by element: contraction-level differences only, |dx|inf <= 1e-12 max|x|."""
+    n, kmax = 6, 1 if L == 1 else 5
+    row, ser = row_op(str(L)), serial_op(L)
+    assert cg.operator_plan(row, kmax) == ("row", "wave") and cg.operator_plan(ser, kmax) == ("serial", "wave")
+    # (instances 1..n: instance 0 at len 1 is the system 0 x = 0 from x0 = 0, a zero residual that tol = 0 divides by)
+    P, Bv, X0 = (np.array(a) for a in zip(*[stencil(L, i) for i in range(1, n + 1)]))
+    xr, nr, wr = cg.gmres_user(row, X0, Bv, kmax, 0.0, P)
+    xs, ns, ws = cg.gmres_user(ser, X0, Bv, kmax, 0.0, P)
+    err = np.max(np.abs(xr - xs))
+    print(f"len {L}: |x_row - x_serial|inf {err:.3e} (bound {1e-12 * np.max(np.abs(xs)):.3e})")
+    assert err <= 1e-12 * np.max(np.abs(xs))
+    assert np.array_equal(nr, ns) and np.array_equal(wr, ws)
+    x, n_ax, why = cg.gmres_user(row, X0, Bv, 30, 1e-6, P)
+    if L == 1:
+        # One product, then h(1,0) = |w - (v0.w) v0| is 0 up to the rounding of v0 = r / |r|: "Breakdown" (gmres.hpp:63)
+        # where it is below DBL_EPSILON, else convergence at k = 0 (:93) with an empty triangular solve.  x is untouched
+        # either way.
+        assert np.array_equal(x, X0) and np.all(n_ax == 1)
+        assert np.all((why == cg.EXIT_BREAKDOWN) | (why == cg.EXIT_CONVERGED))
+        return
+    assert np.all(wr == cg.EXIT_NATURAL) and np.all(nr == kmax)
+    for i in range(n):
+        res = np.linalg.norm(dense_stencil(L, P[i]) @ x[i] - Bv[i]) / np.linalg.norm(Bv[i])
+        assert res < 1e-5, (L, i, res)
+
+
+@pytest.mark.gpu
+def test_lane_path_both_forms_vs_the_reference():
+    """len 840: beyond one wavefront's LDS, the one-lane-per-system kernel (gmres_op_kernel) — the serial form from
+    k_max = 20, the row form from k_max = 21 (see the module docstring) — against the reference's records."""
+    rows = fixture_840()
+    P, Bv, X0 = (np.array(a) for a in zip(*[stencil(840, i) for i in range(2)]))
+    row, ser = row_op("840"), serial_op(840)
+    seen = set()
+    for oid, kmax, plan in ((ser, 20, ("serial", "lane")), (row, 20, ("row", "wave")), (ser, 21, ("serial", "lane")),
+                            (row, 21, ("row", "lane"))):
+        assert cg.operator_plan(oid, kmax) == plan
+        seen.add(plan)
+        x, n_ax, why = cg.gmres_user(oid, X0, Bv, kmax, 0.0, P)
+        ref = rows[rows[:, 1] == kmax][:, 3:]
+        err, scale = np.max(np.abs(x - ref)), np.max(np.abs(ref))
+        print(f"len 840 k_max {kmax} {plan}: |dx|inf {err:.3e} (bound {1e-9 * scale:.3e})")
+        assert err <= 1e-9 * scale, (plan, kmax, err)
+        assert np.all(n_ax == kmax) and np.all(why == cg.EXIT_NATURAL)
+    assert ("serial", "lane") in seen and ("row", "lane") in seen
+
+
+@pytest.mark.gpu
+def test_exits_on_the_row_path():
+    L, kmax, tol = 40, 20, 1e-9
+    oid = row_op("convdiff")
+    assert cg.operator_plan(oid, kmax) == ("row", "wave")
+    P, Bv, X0 = (np.array(a) for a in zip(*[scenario("convdiff", i) for i in range(3)]))
+    # a zero right-hand side leaves at the residual test with x untouched (gmres.hpp:39-41)
+    x0 = np.zeros((3, L))
+    x, n_ax, why = cg.gmres_user(oid, x0, np.zeros((3, L)), 5, 1e-6, P)
+    assert np.array_equal(x, x0) and np.all(n_ax == 0) and np.all(why == cg.EXIT_SMALL_RESIDUAL)
+    # a NaN in one instance's b ends that instance alone
+    x_ok, n_ok, why_ok = cg.gmres_user(oid, X0, Bv, kmax, tol, P)
+    bad = Bv.copy()
+    bad[1, 7] = np.nan
+    x, n_ax, why = cg.gmres_user(oid, X0, bad, kmax, tol, P)
+    assert why[1] == cg.EXIT_NONFINITE and np.all(np.isnan(x[1]))
+    for i in (0, 2):
+        assert np.array_equal(x[i], x_ok[i]) and n_ax[i] == n_ok[i] and why[i] == why_ok[i]
+        assert np.all(np.isfinite(x[i]))
+
+
+@pytest.mark.gpu
+def test_facade_gmres_subclass_with_a_row_operator(tmp_path):
+    """tests/user_models/gmres_main.cpp (a Gmres subclass, unchanged) with the plugin of ConvDiffRowOp: the facade needs
+    no code for the row form — the plugin decides."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    so = plugin.build_operator(ROW_OPS, "ConvDiffRowOp", name="convdiff_row")
+    lib_dir = os.path.join(ROOT, "cgmres_cpp_amd", "lib")
+    exe = tmp_path / "gmres_main"
+    subprocess.run(["g++", "-O2", "-std=c++17", f"-I{ROOT}/include", f"-I{UM}", os.path.join(UM, "gmres_main.cpp"),
+                    f"-L{lib_dir}", f"-Wl,-rpath,{lib_dir}", "-lcgmres_hip", "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe), so], check=True, capture_output=True, text=True).stdout
+    got = np.array([[float(v) for v in l.split()] for l in out.strip().split("\n") if l[0].isdigit()])
+    ref = fixture("convdiff")
+    assert got.shape == ref.shape and np.max(np.abs(got[:, 3:] - ref[:, 3:])) <= 1e-9 * np.max(np.abs(ref[:, 3:]))

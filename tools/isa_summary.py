@@ -3,6 +3,12 @@
 traffic and AGPR copies sit — inside a loop block (the stage loops, the Gram-Schmidt rounds) or in straight-line code.
 
     python tools/isa_summary.py [--out profiles/r02_isa_summary.md] [pattern]
+    python tools/isa_summary.py --operator tests/user_models/gmres_row_ops.hpp ConvDiffRowOp150
+
+The second form summarises the two kernels of an OPERATOR plugin (csrc/user_operator.hip.h: gmres_wave_kernel,
+gmres_op_kernel) for the struct named: per loop depth (1 = the Arnoldi loop, 2 = the Gram-Schmidt rounds and whatever
+loops the operator brings) the instruction count and how many of them are ds_ (LDS), flat_ (an LDS or HBM access whose
+address space the compiler could not prove: an operand that left LDS addressing), scratch_ and global_ accesses.
 
 For every inst_*.hip translation unit: hipcc -S --cuda-device-only -Rpass-analysis=kernel-resource-usage, then per
 kernel: VGPR / AGPR / SGPR, VGPR+SGPR spill counts, scratch bytes per lane (compiler remarks), the number of
@@ -100,6 +106,48 @@ def scan(body):
 EXTRA = []
 
 
+def operator_summary(header, cls):
+    from cgmres_cpp_amd.plugin import OP_TEMPLATE
+    os.makedirs(TMP, exist_ok=True)
+    src = os.path.join(TMP, "op_" + re.sub(r"\W", "_", cls) + ".hip")
+    with open(src, "w") as f:
+        f.write(OP_TEMPLATE.format(header=os.path.abspath(header), glue=os.path.join(CSRC, "user_operator.hip.h"), cls=cls))
+    asm, rp = compile_tu(src)
+    rm = remarks(rp)
+    names = [m.group(1) for m in re.finditer(r"^(_Z\w+):", asm, re.M) if "gmres_" in m.group(1)]
+    dm = demangle(names) if names else {}
+    kinds = ("ds_", "flat_", "scratch_", "global_")
+    lines = [f"# ISA summary of the operator plugin of `{cls}` ({os.path.basename(header)}; gfx950, hipcc -O3)", "",
+             "Per loop depth: instructions, of which ds_/flat_/scratch_/global_ accesses (depth 0 = straight-line code, "
+             "1 = the Arnoldi loop, 2+ = loops inside it).", "",
+             "| kernel | VGPR | SGPR | scratch B/lane | instrs | depth 0 | depth 1 | depth 2+ |", "|---|---|---|---|---|---|---|---|"]
+    for name in names:
+        m = re.search(r"^" + re.escape(name) + r":.*?\.end_amdhsa_kernel", asm, re.S | re.M)
+        if not m:
+            continue
+        lv = [dict(n=0, **{k: 0 for k in kinds}) for _ in range(3)]
+        depth = 0
+        for line in m.group(0).split("\n"):
+            t = line.strip()
+            if re.match(r"^\.LBB\d+_\d+:", t):
+                depth = 0
+            elif t.startswith(";"):
+                d = re.search(r"Depth=(\d+)", t)
+                if d:
+                    depth = max(depth, int(d.group(1)))
+            elif t and not t.startswith(".") and not t.endswith(":"):
+                c = lv[min(depth, 2)]
+                c["n"] += 1
+                for k in kinds:
+                    c[k] += t.startswith(k)
+        r = rm.get(name, {})
+        short = re.sub(r"cgm::|void |\(.*", "", dm.get(name, name))
+        cell = lambda c: f"{c['n']} (" + "/".join(str(c[k]) for k in kinds) + ")"
+        lines.append(f"| `{short}` | {r.get('vgpr')} | {r.get('sgpr')} | {r.get('scratch')} | {sum(c['n'] for c in lv)} | "
+                     f"{cell(lv[0])} | {cell(lv[1])} | {cell(lv[2])} |")
+    return "\n".join(lines) + "\n"
+
+
 def main():
     args = [a for a in sys.argv[1:]]
     out_path = None
@@ -107,6 +155,14 @@ def main():
         i = args.index("--out")
         out_path = args[i + 1]
         del args[i:i + 2]
+    if "--operator" in args:
+        i = args.index("--operator")
+        sys.path.insert(0, ROOT)
+        text = operator_summary(args[i + 1], args[i + 2])
+        if out_path:
+            open(os.path.join(ROOT, out_path) if not os.path.isabs(out_path) else out_path, "w").write(text)
+        print(text)
+        return
     for a in list(args):
         if a.startswith("-D"):
             EXTRA.append(a)
