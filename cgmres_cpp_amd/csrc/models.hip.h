@@ -65,6 +65,12 @@ __device__ __forceinline__ double rint_t(double a) { return __builtin_rint(a); }
 __device__ __forceinline__ float rint_t(float a) { return __builtin_rintf(a); }
 __device__ __forceinline__ double maxabs_t(double m, double a) { return __builtin_fmax(m, __builtin_fabs(a)); }
 __device__ __forceinline__ float maxabs_t(float m, float a) { return __builtin_fmaxf(m, __builtin_fabsf(a)); }
+// |a| as fabs — a source modifier of the consuming instruction, where `a < 0 ? -a : a` is a compare, a select and a move
+// (the compiler may not merge those: -0 and NaN).  Every use is an operand of a comparison or of fmax (the rotation
+// guard, the Newton convergence test, the breakdown and tolerance tests of the solvers): no stored value sees the sign
+// of a zero or a NaN's payload.
+__device__ __forceinline__ double abs_t(double a) { return __builtin_fabs(a); }
+__device__ __forceinline__ float abs_t(float a) { return __builtin_fabsf(a); }
 // ordered-as-integers view of a NON-NEGATIVE value (a running maximum without the canonicalising v_max of fmax)
 __device__ __forceinline__ int nonneg_bits(double z) { return __double2hiint(z); }
 __device__ __forceinline__ int nonneg_bits(float z) { return __float_as_int(z); }

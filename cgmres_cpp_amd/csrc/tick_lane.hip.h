@@ -176,10 +176,6 @@ template <>
 __device__ __forceinline__ float sqrt_t<float>(float a) {
   return ::sqrtf(a);
 }
-template <class T>
-__device__ __forceinline__ T abs_t(T a) {
-  return a < T(0) ? -a : a;
-}
 // neither NaN nor +-Inf (one v_cmp_class on the hardware)
 __device__ __forceinline__ bool finite_t(double a) { return __builtin_isfinite(a); }
 __device__ __forceinline__ bool finite_t(float a) { return __builtin_isfinite(a); }

@@ -51,7 +51,7 @@
 #include "stage_own.hip.h"
 #include "dpp.hip.h"
 #include "models.hip.h"
-#include "tick_lane.hip.h"  // sqrt_t / abs_t / FOut
+#include "tick_lane.hip.h"  // sqrt_t / FOut
 
 namespace cgm {
 
@@ -2098,9 +2098,14 @@ struct WgCtx {
     const T a = T(1) - dtau * M::As, bs = dtau * M::Bs;
     T dx0[SPL], dx2[SPL];
     {
-      T e0 = T(0), e2 = T(0);
+      // (the first two stages written out — from a zero difference the first leaves (0, bs du), and the second still
+      // finds e0 = 0: left in the loop, their operations on literal zeros stay in the instruction stream, there being
+      // no fast-math to fold them)
+      static_assert(SPL >= 2, "two stages of the fold are written out");
+      const T e2_0 = bs * du[0];
+      T e0 = dtau * e2_0, e2 = fma_t(a, e2_0, bs * du[1]);
 #pragma unroll
-      for (int q = 0; q < SPL; ++q) {
+      for (int q = 2; q < SPL; ++q) {
         const T n0 = fma_t(dtau, e2, e0);
         e2 = fma_t(a, e2, bs * du[q]);
         e0 = n0;
@@ -2166,7 +2171,9 @@ struct WgCtx {
       // defects of the stage equations (the stage after the lane's last one belongs to the next lane) and the local
       // composition of the linearised stage maps  D -> D + [[0, dq], [j, eq]] (I + D)  in the D-form of wave_scan.hip.h
       const T yn1 = dpp_row_zero_fill<0x101>(y1[0]), yn3 = dpp_row_zero_fill<0x101>(y3[0]);  // row_shl:1
-      T D[4] = {T(0), T(0), T(0), T(0)}, c[2] = {T(0), T(0)};
+      // (from D = 0, c = 0 the first stage leaves its own map, and the second still finds D[0] = 0: written out, like
+      // the first stages of the x0/x2 fold)
+      T D[4], c[2];
 #pragma unroll
       for (int q = 0; q < SPL; ++q) {
         // model.hpp:41 and its derivative in x1
@@ -2177,9 +2184,14 @@ struct WgCtx {
         const T r1 = t1 - (q + 1 < SPL ? y1[q + 1 < SPL ? q + 1 : 0] : yn1);
         const T r3 = t3 - (q + 1 < SPL ? y3[q + 1 < SPL ? q + 1 : 0] : yn3);
         c0q[q] = tr[q] ? r1 : T(0), c1q[q] = tr[q] ? r3 : T(0);
-        const T n00 = fma_t(dq[q], D[2], D[0]);
+        if (q == 0) {
+          D[0] = T(0), D[1] = dq[0], D[2] = jq[0], D[3] = eq[0], c[0] = c0q[0], c[1] = c1q[0];
+          continue;
+        }
+        const bool z = q == 1;  // D[0] is the first stage's zero
+        const T n00 = z ? dq[q] * D[2] : fma_t(dq[q], D[2], D[0]);
         const T n01 = fma_t(dq[q], D[3], D[1] + dq[q]);
-        const T n10 = fma_t(eq[q], D[2], fma_t(jq[q], D[0], D[2] + jq[q]));
+        const T n10 = fma_t(eq[q], D[2], z ? D[2] + jq[q] : fma_t(jq[q], D[0], D[2] + jq[q]));
         const T n11 = fma_t(eq[q], D[3], fma_t(jq[q], D[1], D[3] + eq[q]));
         const T m0 = fma_t(dq[q], c[1], c[0] + c0q[q]);
         const T m1 = fma_t(eq[q], c[1], fma_t(jq[q], c[0], c[1] + c1q[q]));
@@ -2257,7 +2269,22 @@ struct WgCtx {
   // ahead and its buffer refilled right after its round, so each load has DEPTH-1 rounds (~1000 cycles) to arrive.
 
   // One round of modified Gram-Schmidt (gmres.hpp:52-58): h(i,k) = <v_i, w> into Hk[i], w -= h(i,k) v_i
-  __device__ __forceinline__ void mgs_round(T* w, T* Hk, const T* vi, int i) const {
+  // PARKED: the row lives in the accumulator file (the kept rows and the ring buffers of the row-Newton kernel).  It is
+  // brought into arithmetic registers ONCE, for the dot product and the update: left to itself the allocator
+  // re-materialises the copy for the update — 2 NVEC v_accvgpr_read per pass, twice per round, all of them issue slots
+  // of a wave that has its SIMD to itself.  An opaque copy cannot be re-materialised.
+  template <bool PARKED = false>
+  __device__ __forceinline__ void mgs_round(T* w, T* Hk, const T* vrow_i, int i) const {
+    T row[NVEC];
+    const T* vi = vrow_i;
+    if constexpr (PARKED) {
+#pragma unroll
+      for (int m = 0; m < NVEC; ++m) {
+        row[m] = vrow_i[m];
+        asm volatile("" : "+v"(row[m]));
+      }
+      vi = row;
+    }
     T pa = 0, pb = 0;  // two partial sums: the fp64 FMA chain is latency-bound (8 cycles/op dependent)
 #pragma unroll
     for (int m = 0; m < NVEC; m += 2) {
@@ -2571,8 +2598,9 @@ struct WgCtx {
         auto round = [&](const T* vi, int i) { mgs_round(w, Hk, vi, i); };
         if (preload) {
           if constexpr (COMPACT) {
-            keep_rows(k, round);
-            if (k > NKEEP) ring_walk<false>(vbuf, NKEEP, k, round, stamp_row_wait, stamp_ring_round);
+            auto round_parked = [&](const T* vi, int i) { mgs_round<true>(w, Hk, vi, i); };
+            keep_rows(k, round_parked);
+            if (k > NKEEP) ring_walk<false>(vbuf, NKEEP, k, round_parked, stamp_row_wait, stamp_ring_round);
           } else {
             ring_cases(vbuf, k, round, stamp_row_wait, stamp_ring_round);
           }

@@ -4,11 +4,14 @@ opens the GPU: every step is a fresh child process under a time limit, and the f
 out of time ends the job).
 
     python tools/gs_evidence.py --out DIR --libs name=path[,stamps=path] ... [--rounds 3] [--budget 600] [--skip pmc,stamps,ab,trace]
+                                [--pmc-libs a,b] [--pmc-counters SQ_INSTS_VALU,SQ_INSTS_SALU,...]
 
 For every library (the first one is the base of the comparisons):
   pmc     two rocprofv3 --pmc passes of the plain bench command, each a run of its own with the program directly after
           `--` and no tracing: the instruction-cache / instruction-fetch group, then the L2 (TCC) hit / miss / request
           counters the available-counter list offers.  Reduced to per wave and tick for the tick kernel.
+          With --pmc-counters: ONE pass of exactly the counters named instead (two, half the names each, if the SQ does
+          not hold them in one), per wave and tick — the instructions a wave actually issues.
   stamps  tools/phase_stamps.py on the library's -DCGM_STAMPS twin (stamps=...), with the split of the MGS rounds.
   ab      bench.py --steps 200 --warmup 50 --reps 5, the libraries interleaved, --rounds runs each; the first round also
           dumps the outputs, which are compared with == against the base library's.
@@ -118,6 +121,18 @@ def pmc(name, lib, tcc):
     return out
 
 
+def pmc_named(name, lib, names):
+    got = pmc_pass(f"pmc_{name}_named", names, lib)
+    if got is None:
+        got = {}
+        h = (len(names) + 1) // 2
+        for i, grp in enumerate((names[:h], names[h:])):
+            got.update(pmc_pass(f"pmc_{name}_named{i}", grp, lib) or {})
+    return dict(library_sha256_16=sha16(lib), launches=next((v["launches"] for v in got.values()), None),
+                waves_per_launch=next((v["waves"] for v in got.values()), None),
+                per_wave_and_tick={k: v["per_launch"] / max(1, v["waves"]) / TICKS_PER_LAUNCH for k, v in got.items()})
+
+
 def stamps(name, lib):
     rc, txt = run([sys.executable, os.path.join(ROOT, "tools", "phase_stamps.py"), "--variant=2", "--lib=" + lib], f"stamps_{name}.txt", 240)
     rows = {}
@@ -146,14 +161,19 @@ def main():
     RESULT["libraries"] = {n: dict(path=os.path.relpath(p, ROOT), library_sha256_16=sha16(p)) for n, p in libs}
     base = libs[0][0]
 
-    if "pmc" not in skip:
+    pmc_libs = [l for l in libs if l[0] in (opt("--pmc-libs") or ",".join(n for n, _ in libs[:2])).split(",")]
+    if "pmc" not in skip and opt("--pmc-counters"):
+        RESULT["counters"] = {}
+        for name, lib in pmc_libs:
+            RESULT["counters"][name] = pmc_named(name, lib, opt("--pmc-counters").split(","))
+            save()
+    elif "pmc" not in skip:
         _, avail = run(["rocprofv3", "--list-avail"], "avail.log", 120)
         open(os.path.join(OUT, "avail.txt"), "w").write(avail)
         names = set(re.findall(r"\bTCC_(?:HIT|MISS|REQ)[A-Za-z_]*\b", avail))
         tcc = [("TCC_%s_sum" % k) if ("TCC_%s_sum" % k) in names else "TCC_" + k for k in ("HIT", "MISS", "REQ")]
         RESULT["tcc_counters_offered"] = sorted(names)
         RESULT["counters"] = {}
-        pmc_libs = [l for l in libs if l[0] in (opt("--pmc-libs") or ",".join(n for n, _ in libs[:2])).split(",")]
         for name, lib in pmc_libs:
             RESULT["counters"][name] = pmc(name, lib, tcc)
             save()

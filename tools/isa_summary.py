@@ -4,11 +4,18 @@ traffic and AGPR copies sit — inside a loop block (the stage loops, the Gram-S
 
     python tools/isa_summary.py [--out profiles/r02_isa_summary.md] [pattern]
     python tools/isa_summary.py --operator tests/user_models/gmres_row_ops.hpp ConvDiffRowOp150
+    python tools/isa_summary.py --blocks "PendulumDev<double>, double, 16, 10, false, 1, 1" [--csrc DIR] [--out FILE]
 
 The second form summarises the two kernels of an OPERATOR plugin (csrc/user_operator.hip.h: gmres_wave_kernel,
 gmres_op_kernel) for the struct named: per loop depth (1 = the Arnoldi loop, 2 = the Gram-Schmidt rounds and whatever
 loops the operator brings) the instruction count and how many of them are ds_ (LDS), flat_ (an LDS or HBM access whose
 address space the compiler could not prove: an operand that left LDS addressing), scratch_ and global_ accesses.
+
+The third form lists ONE kernel (the first whose demangled name contains the substring) basic block by basic block, in
+program order: loop depth, instruction count and how many of the instructions are v_accvgpr_* copies, v_readlane /
+v_writelane, DPP moves, ds_* (LDS), global_* accesses and floating-point arithmetic with a literal-zero operand (an
+operation the compiler could not fold: no fast-math).  --csrc points it at the sources of another checkout (the parent
+of a change), so that two listings can be set side by side.
 
 For every inst_*.hip translation unit: hipcc -S --cuda-device-only -Rpass-analysis=kernel-resource-usage, then per
 kernel: VGPR / AGPR / SGPR, VGPR+SGPR spill counts, scratch bytes per lane (compiler remarks), the number of
@@ -105,6 +112,73 @@ def scan(body):
 
 EXTRA = []
 
+FP_ARITH = re.compile(r"^v_(pk_)?(fma|fmac|mad|mac|add|sub|mul|max|min)\w*_f(16|32|64)")
+
+
+def block_listing(asm, name, short, r):
+    """One line per basic block of the kernel `name`, in program order."""
+    m = re.search(r"^" + re.escape(name) + r":.*?\.end_amdhsa_kernel", asm, re.S | re.M)
+    kinds = ("acc", "lane", "dpp", "ds", "global", "zero")
+    blocks, cur = [], dict(label="(entry)", depth=0, n=0, **{k: 0 for k in kinds})
+    blocks.append(cur)
+    n_scratch = len(re.findall(r"^\s*scratch_", m.group(0), re.M))
+    for line in m.group(0).split("\n")[1:]:
+        t = line.split(";")[0].strip() if not line.strip().startswith(";") else line.strip()
+        mm = re.match(r"^\.(LBB\d+_\d+):", t)
+        if mm:
+            cur = dict(label="_" + mm.group(1).split("_")[1], depth=0, n=0, **{k: 0 for k in kinds})
+            blocks.append(cur)
+            continue
+        if t.startswith(";"):
+            d = re.search(r"Depth=(\d+)", t)
+            if d:
+                cur["depth"] = max(cur["depth"], int(d.group(1)))
+            continue
+        if not t or t.startswith(".") or t.endswith(":"):
+            continue
+        if t.startswith("s_endpgm"):
+            cur["n"] += 1
+            break
+        op = t.split()[0]
+        operands = [o.strip() for o in t[len(op):].split(",")]
+        cur["n"] += 1
+        cur["acc"] += op.startswith("v_accvgpr")
+        cur["lane"] += op.startswith(("v_readlane", "v_writelane"))
+        cur["dpp"] += op.startswith("v_mov") and any(k in t for k in ("row_", "quad_perm", "wave_", "_dpp"))
+        cur["ds"] += op.startswith("ds_")
+        cur["global"] += op.startswith("global_")
+        cur["zero"] += bool(FP_ARITH.match(op)) and "0" in operands[1:]
+    tot = {k: sum(b[k] for b in blocks) for k in ("n",) + kinds}
+    lines = [f"# Basic blocks of `{short}` (gfx950, hipcc -O3; tools/isa_summary.py --blocks)", "",
+             "Program order.  depth: loop nest level (1 = ticks, 2 = Arnoldi iterations, 3+ = loops inside one).  acc = v_accvgpr_*,",
+             "lane = v_readlane/v_writelane, dpp = DPP moves, zero0 = fp arithmetic with a literal-zero operand.", "",
+             f"VGPR {r.get('vgpr')}, AGPR {r.get('agpr')}, VGPR spill {r.get('vgpr_spill')}, SGPR spill {r.get('sgpr_spill')}, "
+             f"scratch {r.get('scratch')} B/lane, scratch_ instructions {n_scratch}", "",
+             f"total: {tot['n']} instructions, acc {tot['acc']}, lane {tot['lane']}, dpp {tot['dpp']}, ds {tot['ds']}, "
+             f"global {tot['global']}, zero0 {tot['zero']}", "",
+             "block  depth  instrs    acc   lane    dpp     ds global  zero0"]
+    for b in blocks:
+        lines.append(f"{b['label']:<6} {b['depth']:>5} {b['n']:>7} " + " ".join(f"{b[k]:>6}" for k in kinds))
+    return "\n".join(lines) + "\n"
+
+
+def blocks_main(sub, out_path):
+    srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.startswith("inst_") and f.endswith(".hip"))
+    with ThreadPoolExecutor(min(6, len(os.sched_getaffinity(0)))) as ex:
+        res = list(ex.map(compile_tu, srcs))
+    for asm, rp in res:
+        names = [m.group(1) for m in re.finditer(r"^(_Z\w+):", asm, re.M) if "_kernel" in m.group(1)]
+        dm = demangle(names) if names else {}
+        for name in names:
+            if sub in dm[name]:
+                short = re.sub(r"cgm::|void |\(cgm::WgParams<\w+>\)|\(cgm::LaneParams<\w+>\)", "", dm[name])
+                text = block_listing(asm, name, short, remarks(rp).get(name, {}))
+                if out_path:
+                    open(os.path.join(ROOT, out_path) if not os.path.isabs(out_path) else out_path, "w").write(text)
+                print(text)
+                return
+    sys.exit(f"no kernel whose name contains {sub!r}")
+
 
 def operator_summary(header, cls):
     from cgmres_cpp_amd.plugin import OP_TEMPLATE
@@ -155,6 +229,15 @@ def main():
         i = args.index("--out")
         out_path = args[i + 1]
         del args[i:i + 2]
+    if "--csrc" in args:
+        global CSRC
+        i = args.index("--csrc")
+        CSRC = os.path.abspath(args[i + 1])
+        del args[i:i + 2]
+    if "--blocks" in args:
+        i = args.index("--blocks")
+        blocks_main(args[i + 1], out_path)
+        return
     if "--operator" in args:
         i = args.index("--operator")
         sys.path.insert(0, ROOT)
