@@ -86,6 +86,14 @@ def lib(which="oracle"):
     return _libs[which]
 
 
+def register_library(name, path):
+    """Make a library with the entry points of oracle/orc_api.h, built elsewhere (another flavour of liboracle.so),
+    available as Controller(..., which=name)."""
+    if name in ("oracle", "ref"):
+        raise ValueError(f"{name} is one of the checker libraries")
+    _libs[name] = _load(path)
+
+
 def have_ref():
     return os.path.exists(REF_SO)
 

@@ -1,5 +1,5 @@
 // CPU probe of the wg planner (csrc/wg_plan.hip.h) and of the LDS carve-up it sizes (WgLds, csrc/tick_wg.hip.h) for the
-// six built-in (model, dtype) pairs; built and loaded by tests/test_wg_plan.py.  No kernel is instantiated and no HIP
+// six built-in (model, dtype) pairs; built and loaded by tests/plan_probe.py.  No kernel is instantiated and no HIP
 // call is made: it runs on a machine without a GPU.
 #include <cstring>
 

@@ -1,0 +1,273 @@
+"""Which shapes of tests/kernel_classes.py can hold a kernel to the oracle at all: measured on the reference side, on
+the CPU, without a GPU and without the reference tree.
+
+    python tools/kernel_case_admission.py            # re-measure every case of CASES and compare with its recorded columns
+    python tools/kernel_case_admission.py --select   # choose members A and B of every class; print the CASES block
+    python tools/kernel_case_admission.py --select --write   # ... and put it into tests/kernel_classes.py
+    python tools/kernel_case_admission.py MODEL DTYPE DV KMAX   # figures of one candidate
+
+Method (that of FP32_SPREAD in tests/test_gpu_tuning.py): the oracle is built a second time into a temporary directory
+through oracle/Makefile's CXXFLAGS override: the Makefile's own flags with -ffp-contract=fast -mfma in place of
+-ffp-contract=off (contraction does nothing on x86-64 unless the target has a fused multiply-add, so the flavour names
+one).  Both builds are the same statements in the same order.  The 20 seeded instances of orc.batch_scenario that the
+GPU test runs are stepped for 6 ticks, the contracted build teacher-forced from the plain build's controller state and
+x every tick, with tol = 1e-6 and with tol = 0.  (A spread taken over the first six instances alone was exceeded by the
+two builds themselves on the seventh: pendulum fp32, dv 105, k_max 20, dUdt' 7.4e-4 over six, 1.3e-3 over twenty.)  What
+two roundings of the reference's own statements disagree on, no kernel can be held to.
+
+Admitted for a tolerance mode:
+    fp64   every Arnoldi count and exit reason equal, |du| <= 1e-10 * max(1, |u|), |ddUdt'| <= 1e-8 * max(1, |dUdt'|): a
+           tenth of the device bounds (1e-9, 1e-7).  And, for the device loop of the GPU test: the two
+           builds free-running for 12 ticks from the seeded start end within 1e-8 on u and x (a tenth of its 1e-7) with
+           equal counts and reasons at the last tick; with tol = 0 the plain build runs k_max iterations on every tick
+           (the GPU test asserts exactly that of the device).
+    fp32   the figures are finite (the device's counts are not compared in fp32).  A spread of u or of U' above
+           1e-4 / 8, or of dUdt' above 5e-3 / 8 relative, is recorded in fp32_spread, each quantity with its own
+           figure, and the device bound of that quantity becomes 8 x its spread.  The device loop's bounds are fixed
+           (1e-4 on u, x and U, 2e-3 relative on dUdt), so the free-running builds must end within an eighth of them:
+           the same margin for the device's other association order.
+A candidate that is not admitted with tol = 1e-6 is passed over for the next member of its class in the same ordering;
+one that is admitted with tol = 1e-6 only gets fixed_k_ok = False.  kernel_classes.DEVICE_MISSES lists the shapes that were
+admitted here and that a kernel then missed on the device with the lane mapping inside its bounds: findings about that
+kernel, passed over in the same way and named in the table."""
+import math
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import kernel_classes as kc  # noqa: E402
+import plan_probe  # noqa: E402
+from oracle import orc  # noqa: E402
+
+N_INST, N_TICKS, LOOP_TICKS = 20, 6, 12
+TOLS = (1e-6, 0.0)
+F64_U, F64_D, F64_LOOP = 1e-10, 1e-8, 1e-8
+F32_U, F32_D, F32_LOOP, F32_LOOP_D = 1e-4 / 8, 5e-3 / 8, 1e-4 / 8, 2e-3 / 8
+PLAIN, FAST = "-ffp-contract=off", "-ffp-contract=fast -mfma"
+
+
+def fast_flags():
+    """oracle/Makefile's default CXXFLAGS with the contraction switched on"""
+    for line in open(os.path.join(orc.HERE, "Makefile")):
+        if line.startswith("CXXFLAGS") and PLAIN in line:
+            return line.split("=", 1)[1].strip().replace(PLAIN, FAST)
+    sys.exit("oracle/Makefile: no default CXXFLAGS with " + PLAIN)
+
+
+def build_fast_flavour():
+    """oracle/'s sources copied to a temporary directory and built there with fast_flags(); registers it as orc's
+    library "fast".  Returns the directory (the caller removes it)."""
+    if "fma" not in open("/proc/cpuinfo").read().split():
+        sys.exit("this CPU has no fused multiply-add: the contracted flavour cannot run here")
+    if not os.path.exists(orc.ORACLE_SO):
+        orc.build(ref=False)
+    tmp = tempfile.mkdtemp(prefix="oracle_fast_")
+    for f in os.listdir(orc.HERE):
+        if f.endswith((".cpp", ".hpp", ".h")) or f == "Makefile":
+            shutil.copy(os.path.join(orc.HERE, f), tmp)
+    subprocess.run(["make", "-C", tmp, "oracle", "CXXFLAGS=" + fast_flags()], check=True, stdout=subprocess.DEVNULL)
+    orc.register_library("fast", os.path.join(tmp, "liboracle.so"))
+    return tmp
+
+
+def worse(a, b):
+    return max(a, b) if math.isfinite(b) else math.inf  # (max() drops a NaN)
+
+
+def measure(model, dtype, dv, k_max, tol):
+    """(su, sU, sd, agree): worst spread of u, U' and dUdt' between the two builds (fp64: relative to max(1, |.|) of the
+    plain build's vector; fp32: u and U' absolute, dUdt' relative, as the device bounds are) and whether all counts and
+    reasons agreed."""
+    dt_name = kc.DTYPE_NAMES[dtype]
+    f32 = dtype == 1
+    x0, u0, p = orc.batch_scenario(model, N_INST)
+    su = sU = sd = 0.0
+    agree = True
+    for i in range(N_INST):
+        a = orc.Controller(model, dv, k_max, tol, dt_name)
+        b = orc.Controller(model, dv, k_max, tol, dt_name, which="fast")
+        orc.start_controller(a, x0[i], u0[i], p[i])
+        orc.start_controller(b, x0[i], u0[i], p[i])
+        x = x0[i].astype(np.float32).astype(np.float64) if f32 else x0[i].copy()
+        for _ in range(N_TICKS):
+            t, U, d = a.get_state()
+            b.set_state(t, U, d)
+            ua, ub = a.control(x), b.control(x)
+            _, Ua, da = a.get_state()
+            _, Ub, db = b.get_state()
+            ka, _, ra = a.last_solve()
+            kb, _, rb = b.last_solve()
+            agree = agree and ka == kb and ra == rb
+            scale = (lambda v: 1.0) if f32 else (lambda v: max(1.0, float(np.max(np.abs(v)))))
+            su = worse(su, float(np.max(np.abs(ua - ub))) / scale(ua))
+            sU = worse(sU, float(np.max(np.abs(Ua - Ub))) / scale(Ua))
+            sd = worse(sd, float(np.max(np.abs(da - db))) / max(1.0, float(np.max(np.abs(da)))))
+            if f32:
+                x = (x.astype(np.float32) + a.plant(x, ua).astype(np.float32) * np.float32(a.dt)).astype(np.float64)
+            else:
+                x = x + a.plant(x, ua) * a.dt
+    return su, sU, sd, agree
+
+
+def measure_loop(model, dtype, dv, k_max, tol):
+    """The two builds free-running for LOOP_TICKS ticks from the seeded start (what the device loop of the GPU test is
+    compared with): (worst |du| and |dx| after the last tick, last tick's counts and reasons equal, every count of every
+    tick of the plain build = k_max).  fp32: U joins u and x, and the relative spread of dUdt is returned as well (the
+    quantities test_gpu_closed_loop.test_closed_loop_device_vs_oracle bounds)."""
+    dt_name = kc.DTYPE_NAMES[dtype]
+    npdt = np.float32 if dtype == 1 else np.float64
+    x0, u0, p = orc.batch_scenario(model, N_INST)
+    s, sd, agree, full = 0.0, 0.0, True, True
+    for i in range(N_INST):
+        ends = []
+        for which in ("oracle", "fast"):
+            c = orc.Controller(model, dv, k_max, tol, dt_name, which=which)
+            orc.start_controller(c, x0[i], u0[i], p[i])
+            x = np.array(x0[i], dtype=npdt)
+            for _ in range(LOOP_TICKS):
+                u = c.control(x)
+                x = (x + c.plant(x, u).astype(npdt) * npdt(c.dt)).astype(npdt)
+                full = full and (which == "fast" or c.last_solve()[0] == k_max)
+            ends.append((u, x.astype(np.float64), c.last_solve(), c.get_state()))
+        (ua, xa, la, (_, Ua, da)), (ub, xb, lb, (_, Ub, db)) = ends
+        s = worse(s, max(float(np.max(np.abs(ua - ub))), float(np.max(np.abs(xa - xb)))))
+        if dtype == 1:
+            s = worse(s, float(np.max(np.abs(Ua - Ub))))
+            sd = worse(sd, float(np.max(np.abs(da - db))) / max(1.0, float(np.max(np.abs(da)))))
+        agree = agree and la[0] == lb[0] and la[2] == lb[2]
+    return s, sd, agree, full
+
+
+_cache = {}
+
+
+def admission(model, dtype, dv, k_max):
+    """per tolerance mode: (admitted, figures, fp32 spread triple or None)"""
+    key = (model, dtype, dv, k_max)
+    if key not in _cache:
+        out = []
+        for tol in TOLS:
+            su, sU, sd, agree = measure(model, dtype, dv, k_max, tol)
+            sl, sld, agree_l, full = measure_loop(model, dtype, dv, k_max, tol)
+            finite = all(math.isfinite(v) for v in (su, sU, sd, sl, sld))
+            if dtype == 0:
+                ok = finite and agree and su <= F64_U and sd <= F64_D and agree_l and sl <= F64_LOOP and (tol > 0 or full)
+                spread = None
+            else:
+                ok = finite and sl <= F32_LOOP and sld <= F32_LOOP_D
+                spread = tuple(float("%.2e" % v) if v > lim else None for v, lim in ((su, F32_U), (sU, F32_U), (sd, F32_D)))
+                spread = spread if ok and any(spread) else None
+            out.append((ok, (su, sU, sd, agree, sl, agree_l, full), spread))
+        _cache[key] = out
+    return _cache[key]
+
+
+def figures(adm):
+    return " | ".join("%.1e %.1e %.1e %s, loop %.1e %s%s" % (f[0], f[1], f[2], "agree" if f[3] else "COUNTS DIFFER", f[4],
+                                                            "agree" if f[5] else "COUNTS DIFFER", "" if f[6] else ", early exits")
+                      for _, f, _ in adm)
+
+
+def columns(adm):
+    """(fixed_k_ok, fp32_spread) of an admitted case"""
+    spread = (adm[0][2], adm[1][2] if adm[1][0] else None)
+    return adm[1][0], (spread if any(spread) else None)
+
+
+def pick(rows, cls):
+    """the first member of `rows` admitted with tol = 1e-6 and not among the device misses of class `cls`, and one line per
+    horizon passed over on the way (its k_max values and the figures of the first of them)"""
+    passed = {}
+    for r in rows:
+        adm = admission(*r[:4])
+        miss = kc.DEVICE_MISSES.get(cls, {}).get(r[2:4])
+        if adm[0][0] and not miss:
+            break
+        what = "DEVICE MISS, " + miss + "; reference side" if miss else "not admitted"
+        ks = passed.setdefault((r[2], what), ([], figures(adm)))[0]
+        if r[3] not in ks:
+            ks.append(r[3])
+    else:
+        r = adm = None
+    text = ["dv %d k_max %s %s (k_max %d: %s)" % (dv, ",".join(map(str, ks)), what, ks[0], fig) for (dv, what), (ks, fig) in passed.items()]
+    return r, adm, text
+
+
+def select():
+    lib = plan_probe.probe()
+    mem = kc.members(lib)
+    lines = ["CASES = ["]
+    for c in sorted(mem):
+        chosen = []
+        for which, order in (("A", kc.order_a), ("B", kc.order_b)):
+            r, adm, passed = pick(order(mem[c]), c)
+            if r is None:
+                lines.append("    # %s: NO MEMBER ADMITTED" % kc.class_name(c))
+                lines += ["    #   " + t for t in passed[:6]]
+                break
+            if chosen and chosen[0][0][:6] == r[:6]:
+                continue
+            chosen.append((r, adm, passed, which))
+        if len(chosen) == 1 and chosen[0][3] == "A" and kc.order_b(mem[c])[0][:6] == chosen[0][0][:6]:
+            chosen[0] = chosen[0][:3] + ("A = B",)
+        for r, adm, passed, which in chosen:
+            lines += ["    # " + t for t in passed]
+            lines.append("    # %s of %d, lds_bytes %d: %s" % (which, len(mem[c]), r[6], figures(adm)))
+            fixed_k_ok, spread = columns(adm)
+            lines.append("    (%d, %d, %d, %d, %d, %d, %r, %r, %r, %r)," % (r[:6] + (c, r[7], fixed_k_ok, spread)))
+    lines.append("]")
+    return "\n".join(lines)
+
+
+def write_block(text):
+    """the CASES block of tests/kernel_classes.py and the digest behind it"""
+    path = os.path.join(ROOT, "tests", "kernel_classes.py")
+    src = open(path).read()
+    head, rest = src.split("# BEGIN CASES", 1)
+    first, tail = rest.split("\n", 1)[0], rest.split("# END CASES\n", 1)[1]
+    tail = tail.split("\n", 1)[1]  # (the CASES_DIGEST line)
+    scope = {}
+    exec(text, scope)
+    open(path, "w").write(head + "# BEGIN CASES" + first + "\n" + text + "\n# END CASES\nCASES_DIGEST = %r\n" % kc.digest(scope["CASES"]) + tail)
+
+
+def check():
+    """re-measure CASES; 0 when every recorded column is reproduced"""
+    bad = 0
+    for case in kc.CASES:
+        adm = admission(*case[:4])
+        ok = adm[0][0] and columns(adm) == (case[8], case[9]) and case[2:4] not in kc.DEVICE_MISSES.get(case[6], {})
+        bad += not ok
+        print("%-40s %s  %s" % (kc.case_id(case), figures(adm), "ok" if ok else "RECORDED %r, MEASURED %r" % (case[8:10], columns(adm))))
+    print("%d cases, %d not reproduced" % (len(kc.CASES), bad))
+    return 1 if bad else 0
+
+
+def main(argv):
+    tmp = build_fast_flavour()
+    try:
+        if "--select" in argv:
+            text = select()
+            print(text)
+            if "--write" in argv:
+                write_block(text)
+            return 0
+        if len(argv) == 4:
+            m, d, dv, k = (int(a) for a in argv)
+            adm = admission(m, d, dv, k)
+            print(kc.case_id((m, d, dv, k, 2, 0)), figures(adm), "admitted:", [a[0] for a in adm], "fp32_spread:", [a[2] for a in adm])
+            return 0
+        return check()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
