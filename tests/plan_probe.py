@@ -1,6 +1,8 @@
 """The CPU probe of the wg planner as a plain module: tests/plan_probe.hip built with the library's compiler and flags
 into the library's build directory and loaded with ctypes, plus the helpers that drive it.  No GPU call is made and
-nothing is imported from conftest; tests/test_wg_plan.py and tests/kernel_classes.py share it."""
+nothing is imported from conftest; tests/test_wg_plan.py and tests/kernel_classes.py share it.  probe_user() is the
+same for tests/plan_probe_user.hip (user models: cfg.model_id is the index of an alias of
+tests/user_models/shape_models.hpp); plan(), layout() and check_layout() work on either library."""
 import ctypes as C
 import os
 import subprocess
@@ -20,21 +22,41 @@ CONSTS = ["sizeof_T", "ipw", "NSTG", "NU", "tab_bytes", "scan_bytes", "scan2_byt
           "base_array_bytes", "NBASE"]
 PLAN_FULL, PLAN_FH_HBM, PLAN_LEAN = 0, 1, 2
 
-_lib = None
+USER_PROBE_SRC = os.path.join(HERE, "plan_probe_user.hip")
+USER_PROBE_SO = os.path.join(B.LIB_DIR, "wg_plan_probe_user.so")
+USER_MODELS_HPP = os.path.join(HERE, "user_models", "shape_models.hpp")
+
+_libs = {}
+
+
+def _load(src, so, deps):
+    """The probe library of `src`, built on first use and rebuilt when a header or its source is newer."""
+    if so not in _libs:
+        _, hdrs = B.sources()
+        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in hdrs + [src] + deps):
+            os.makedirs(B.LIB_DIR, exist_ok=True)
+            r = subprocess.run([B.HIPCC] + B.CFLAGS + ["-shared", "-o", so, src], capture_output=True, text=True)
+            assert r.returncode == 0, r.stderr[-4000:]
+        _libs[so] = C.CDLL(so)
+        _libs[so].lds_limit.restype = C.c_longlong
+    return _libs[so]
 
 
 def probe():
-    """The loaded probe library, built on first use and rebuilt when a header or its source is newer."""
-    global _lib
-    if _lib is None:
-        _, hdrs = B.sources()
-        if not os.path.exists(PROBE_SO) or any(os.path.getmtime(d) > os.path.getmtime(PROBE_SO) for d in hdrs + [PROBE_SRC]):
-            os.makedirs(B.LIB_DIR, exist_ok=True)
-            r = subprocess.run([B.HIPCC] + B.CFLAGS + ["-shared", "-o", PROBE_SO, PROBE_SRC], capture_output=True, text=True)
-            assert r.returncode == 0, r.stderr[-4000:]
-        _lib = C.CDLL(PROBE_SO)
-        _lib.lds_limit.restype = C.c_longlong
-    return _lib
+    """The loaded probe library of the built-in models."""
+    return _load(PROBE_SRC, PROBE_SO, [])
+
+
+def probe_user():
+    """The loaded probe library of the user models of tests/user_models/shape_models.hpp."""
+    return _load(USER_PROBE_SRC, USER_PROBE_SO, [USER_MODELS_HPP])
+
+
+def alias_info(lib, alias):
+    """dict(dim_x, dim_u, dim_p, NSTG, wave_fits) of alias number `alias` of the user probe"""
+    out = (C.c_int * 5)()
+    assert lib.alias_info(alias, out) == 0
+    return dict(zip(["dim_x", "dim_u", "dim_p", "NSTG", "wave_fits"], out))
 
 
 def config(model, dtype, dv, k_max, batch, variant, flags, tol, **over):
