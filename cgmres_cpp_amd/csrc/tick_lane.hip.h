@@ -17,6 +17,7 @@
 #include <cfloat>
 
 #include "models.hip.h"
+#include "tick_common.hip.h"
 
 namespace cgm {
 
@@ -38,18 +39,7 @@ struct TickParams {
   int dist_inst, meas_inst;
 };
 
-enum FOut { F_PLAIN = 0, F_RHS = 1, F_AX = 2 };
-
-// Optimality residual F(U [+ h v], x, t) — cgmres.hpp:113-162 (+ :168-174 when PERTURB / F_AX).
-//   F_PLAIN: out = F                                   (cgmres.hpp:88)
-//   F_RHS  : out = (F*(1-zeta*h) - Fh) * (1/h)         (cgmres.hpp:91-96)
-//   F_AX   : out = (F - Fh) * (1/h)                    (cgmres.hpp:173-174)
-// The state equation of stage `stage`.  The built-in models do not read the time-varying parameter p in dxdt; a
-// user model compiled through the plugin path (user_model.hip.h) may (Model::dxdt(ret, x, u, p), */model.hpp:36).
-template <class M, class T, class = void>
-struct DxdtUsesP : std::false_type {};
-template <class M, class T>
-struct DxdtUsesP<M, T, std::enable_if_t<M::DXDT_USES_P>> : std::true_type {};
+// The state equation of stage `stage`: with the stage's parameters where the model reads them (DxdtUsesP, tick_common.hip.h)
 template <class M, class T>
 __device__ __forceinline__ void state_eq(T* f, const T* x, const T* u, T* tr, const typename M::Math& mc,
                                          const T* ptau, size_t ld, int stage) {
@@ -166,25 +156,6 @@ __device__ __forceinline__ void ax_lane(const TickParams<T>& P, size_t ld, const
   f_eval_lane<M, T, true, F_AX>(P, ld, A.U, v, xh, P.dtau_h, out, A.Fh, A.traj, A.trig, A.ptau);
 }
 
-template <class T>
-__device__ __forceinline__ T sqrt_t(T a);
-template <>
-__device__ __forceinline__ double sqrt_t<double>(double a) {
-  return ::sqrt(a);
-}
-template <>
-__device__ __forceinline__ float sqrt_t<float>(float a) {
-  return ::sqrtf(a);
-}
-// neither NaN nor +-Inf (one v_cmp_class on the hardware)
-__device__ __forceinline__ bool finite_t(double a) { return __builtin_isfinite(a); }
-__device__ __forceinline__ bool finite_t(float a) { return __builtin_isfinite(a); }
-template <class T>
-__device__ __forceinline__ T quiet_nan();
-template <>
-__device__ __forceinline__ double quiet_nan<double>() { return __builtin_nan(""); }
-template <>
-__device__ __forceinline__ float quiet_nan<float>() { return __builtin_nanf(""); }
 // CGMRES_HIP_EXIT_NONFINITE: a non-finite residual / Arnoldi norm.  The reference tests for neither; every comparison
 // with a NaN is false there, the remaining iterations run on NaNs and the solution vector ends up NaN (include/gmres.hpp:
 // 39-41, 63-65, 93-95 all fall through).  Here the instance stops at once and its solution vector is set to NaN.

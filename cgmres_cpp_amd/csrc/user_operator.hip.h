@@ -23,6 +23,7 @@
 
 #include "ctx_common.hip.h"
 #include "gmres_plan.hip.h"
+#include "tick_common.hip.h"
 #include "tick_lane.hip.h"
 #include "wave_scan.hip.h"
 

@@ -1,15 +1,17 @@
 // Which kernel of the "wg" family (tick_wg.hip.h, tick_wave.hip.h) a controller batch runs on, with how much LDS and
 // where each array sits: plan_wg() decides all of it from the configuration, the CU count of the device and the
-// model's compile-time traits.  It makes no HIP call and touches no global state, and it needs no kernel to be
-// instantiated (only the LDS layouts and the model traits): tests/test_wg_plan.py runs it on the CPU.
+// model's compile-time traits.  It makes no HIP call and touches no global state, and it sees no kernel code — only the
+// LDS layouts (wg_layout.hip.h, wave_ops.hip.h) and the model traits: tests/test_wg_plan.py runs it on the CPU.
 #pragma once
 #include <cstdarg>
 #include <cstdio>
 #include <string>
 
 #include "../../include/cgmres_hip.h"
-#include "tick_wave.hip.h"
-#include "tick_wg.hip.h"
+#include "models.hip.h"
+#include "tick_common.hip.h"  // DxdtUsesP
+#include "wave_ops.hip.h"
+#include "wg_layout.hip.h"
 
 namespace cgm {
 
@@ -197,22 +199,21 @@ int plan_wg(const cgmres_hip_config& cfg, int cus, WgPlanResult* out, std::strin
       if (bytes_x <= kLdsLimit) r.k.nwt = 2, r.lds_bytes = bytes_x;
     }
     if constexpr (Tr::kRowNewton) {
-      // Newton state sweeps.  The base trajectory (NBASE arrays of 8 KB) goes where LDS is idle during the Arnoldi loop
-      // — the stage table, the scratch of the costate scan — and behind everything else for the rest; the kernel is
+      // Newton state sweeps.  The base trajectory (WG_ROW_NBASE arrays of 8 KB) goes where LDS is idle during the Arnoldi
+      // loop — the stage table, the scratch of the costate scan — and behind everything else for the rest; the kernel is
       // taken when all of that fits.
-      using Ctx = WgCtx<M, T, 16, 10, false, 1, 1>;
       const typename LdsX::Extent e = LdsX::extent(cfg.dv, cfg.k_max, Lp, Pp, Hp, PLAN_FULL);
-      const size_t arr = Ctx::base_array_bytes(), tab_cap = LdsX::tab_count(cfg.dv) * sizeof(T);
+      const size_t arr = wg_base_array_bytes<T>(16), tab_cap = LdsX::tab_count(cfg.dv) * sizeof(T);
       size_t end = (bytes_x + 15) & ~size_t(15), in_tab = 0, in_scan = 0;
-      int off[Ctx::NBASE];
-      for (int k = 0; k < Ctx::NBASE; ++k) {
+      int off[WG_ROW_NBASE];
+      for (int k = 0; k < WG_ROW_NBASE; ++k) {
         if ((in_tab + 1) * arr <= tab_cap) off[k] = int(e.tab_off + in_tab++ * arr);
         else if ((in_scan + 1) * arr <= scratch) off[k] = int(e.scan_off + in_scan++ * arr);
         else off[k] = int(end), end += arr;
       }
       if (cfg.dv >= Tr::kRowNewtonMinDv && end <= kLdsLimit) {
         r.k.nwt = 1, r.lds_bytes = end;
-        for (int k = 0; k < Ctx::NBASE; ++k) r.base_off[k] = off[k];
+        for (int k = 0; k < WG_ROW_NBASE; ++k) r.base_off[k] = off[k];
       }
     }
   }

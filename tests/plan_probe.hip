@@ -1,4 +1,4 @@
-// CPU probe of the wg planner (csrc/wg_plan.hip.h) and of the LDS carve-up it sizes (WgLds, csrc/tick_wg.hip.h) for the
+// CPU probe of the wg planner (csrc/wg_plan.hip.h) and of the LDS carve-up it sizes (WgLds, csrc/wg_layout.hip.h) for the
 // six built-in (model, dtype) pairs; built and loaded by tests/plan_probe.py.  No kernel is instantiated and no HIP
 // call is made: it runs on a machine without a GPU.
 #include <cstring>
@@ -39,10 +39,7 @@ void walk(const cgmres_hip_config& c, int plan, long long* out) {
   out[25] = (long long)(Lds::scan_count(c.dv) * sizeof(T)), out[26] = (long long)(Lds::scan2_count(3) * sizeof(T));
   out[27] = (long long)(Lds::scan2_count(4) * sizeof(T)), out[28] = M::TAB_PAD, out[29] = NWT_TABX;
   out[30] = 0, out[31] = 0;
-  if constexpr (WgTraits<M, T>::kRowNewton) {
-    using Ctx = WgCtx<M, T, 16, 10, false, 1, 1>;
-    out[30] = (long long)Ctx::base_array_bytes(), out[31] = Ctx::NBASE;
-  }
+  if constexpr (WgTraits<M, T>::kRowNewton) out[30] = (long long)wg_base_array_bytes<T>(16), out[31] = WG_ROW_NBASE;
 }
 }  // namespace
 

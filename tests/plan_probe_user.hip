@@ -1,4 +1,4 @@
-// CPU probe of the wg planner (csrc/wg_plan.hip.h) and of the LDS carve-up it sizes (WgLds, csrc/tick_wg.hip.h) for USER
+// CPU probe of the wg planner (csrc/wg_plan.hip.h) and of the LDS carve-up it sizes (WgLds, csrc/wg_layout.hip.h) for USER
 // models: plan_wg<UserDev<Model>, double> for the five aliases of tests/user_models/shape_models.hpp, keyed by the
 // alias's index in cfg->model_id (0 Shape110, 1 Shape321, 2 Shape262, 3 Shape431, 4 Shape521).  Same entry points as
 // tests/plan_probe.hip; built and loaded by tests/plan_probe.py.  UserDev is taken from csrc/user_model.hip.h for its

@@ -1,4 +1,4 @@
-"""GPU parity of the row-Newton kernel's Gram-Schmidt ring (csrc/tick_wg.hip.h, gmres(): the first NKEEP = 2 basis rows
+"""GPU parity of the row-Newton kernel's Gram-Schmidt ring (csrc/wg_gmres.hip.h, gmres(): the first NKEEP = 2 basis rows
 stay in registers, the older ones pass through a ring of NBUF = 3 row buffers — one loop of NBUF rounds per trip with a
 clamped, unconditional refill after every round, a peeled tail of fewer than NBUF rounds, and the same loop in the
 x += V y update) at every basis length at which the loop takes another path:

@@ -1,4 +1,4 @@
-"""GPU parity of the STREAMING form of the Krylov row walk (csrc/tick_wg.hip.h: ring_request + ring_walk<true> over two
+"""GPU parity of the STREAMING form of the Krylov row walk (csrc/wg_gmres.hip.h: ring_request + ring_walk<true> over two
 row buffers from row 0, in the Gram-Schmidt rounds and in x += V y, followed by drain_stream) at sizes of a few
 milliseconds.  The rest of the suite reaches this form only at workload size (fp32, N = 100, k_max = 20, B = 8192); the
 compact ring of the row-Newton kernel is pinned by test_gpu_gs_ring.py.
