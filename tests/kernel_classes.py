@@ -34,9 +34,11 @@ passes them over like a shape that is not admitted.
 
 tests/test_kernel_ledger.py (CPU) fails when a class of grid() has no case here, when a case's class is not one the
 grid yields, and when a case no longer resolves to its recorded class and variant_name."""
-import hashlib
+from collections import namedtuple
+from operator import itemgetter
 
-from plan_probe import PLAN_LEAN, config, plan
+import plan_probe
+from class_ledger import CASE_COLUMNS, MEMBER_COLUMNS, order_a, order_b
 
 FLAG_BITS = {"SERIAL_COSTATE": 1, "IPW8": 2, "TWO_PASS_COSTATE": 8, "SERIAL_STATE_SWEEP": 128}
 FLAGS = (0, 1, 2, 8, 128)
@@ -46,6 +48,11 @@ DTYPE_NAMES = ("f64", "f32")
 DV, KMAX = range(1, 108), range(1, 21)
 BATCH, TOL = 16, 1e-6
 CUS = 256  # enters the library's own choice (variant 0) and `binning` only: neither is part of a class
+
+
+# one row of CASES; one configuration of grid() with what the planner makes of it
+Case = namedtuple("Case", "model dtype " + CASE_COLUMNS + " fp32_spread")
+Member = namedtuple("Member", "model dtype " + MEMBER_COLUMNS)
 
 
 # class -> {(dv, k_max): what was seen}
@@ -65,9 +72,13 @@ DEVICE_MISSES = {
 }
 
 
-def resolve(lib, model, dtype, dv, k_max, variant, flags):
+def cfg(model, dtype, dv, k_max, variant, flags, batch=BATCH, tol=TOL):
+    return plan_probe.config(model, dtype, dv, k_max, batch, variant, flags, tol)
+
+
+def resolve(lib, model, dtype, dv, k_max, variant, flags, batch=BATCH, tol=TOL, cus=CUS):
     """The planner's result for one configuration of grid() (with its model and dtype), or None where it refuses."""
-    r, _ = plan(lib, config(model, dtype, dv, k_max, BATCH, variant, flags, TOL), CUS)
+    r, _ = plan_probe.plan(lib, cfg(model, dtype, dv, k_max, variant, flags, batch, tol), cus)
     if r is not None:
         r["model"], r["dtype"] = model, dtype
     return r
@@ -75,7 +86,15 @@ def resolve(lib, model, dtype, dv, k_max, variant, flags):
 
 def class_of(r):
     assert not r["wave"]
-    return (r["model"], r["dtype"], r["ipw"], r["maxm"], int(r["plan"] == PLAN_LEAN), r["par"], r["nwt"], r["plan"], r["cs_chunks"])
+    return (r["model"], r["dtype"], r["ipw"], r["maxm"], int(r["plan"] == plan_probe.PLAN_LEAN), r["par"], r["nwt"], r["plan"], r["cs_chunks"])
+
+
+# the fields of a class, by name
+model_of, dtype_of, ipw, maxm, lean, par, nwt, plan, cs_chunks = (itemgetter(i) for i in range(9))
+
+
+def kind(c):
+    return "wg"
 
 
 def class_name(c):
@@ -87,35 +106,27 @@ def grid():
 
 
 def members(lib):
-    """class -> its members of grid(): (model, dtype, dv, k_max, variant, flags, lds_bytes, variant_name)"""
+    """class -> its members of grid()"""
     out = {}
     for row in grid():
         r = resolve(lib, *row)
         if r is not None:
-            out.setdefault(class_of(r), []).append(row + (r["lds_bytes"], r["variant_name"]))
+            out.setdefault(class_of(r), []).append(Member(*row, r["lds_bytes"], r["variant_name"]))
     return out
 
 
-def order_a(rows):
-    """members with k_max >= 3 by dv, then k_max; behind them (a class may have no other) those with k_max < 3 by dv, the
-    larger k_max first; among configurations of one shape the plain one (no flag, variant 2) first"""
-    return sorted(rows, key=lambda r: (r[3] < 3, r[2], r[3] if r[3] >= 3 else -r[3], r[5], r[4]))
+def orders(c):
+    """the selections of class c: (letter, ordering) pairs"""
+    return (("A", order_a), ("B", order_b))
 
 
-def order_b(rows):
-    """largest lds_bytes, then largest dv, then largest k_max"""
-    return sorted(rows, key=lambda r: (-r[6], -r[2], -r[3], r[5], r[4]))
+def key(r):
+    """the configuration of a case or a member"""
+    return (r.model, r.dtype, r.dv, r.k_max, r.variant, r.flags)
 
 
-def digest(cases):
-    """of the whole table, columns included: CASES_DIGEST is written with the table, so a case that is deleted or edited
-    by hand shows in tests/test_kernel_ledger.py"""
-    return hashlib.sha256(repr(sorted(cases)).encode()).hexdigest()[:16]
-
-
-def case_id(case):
-    m, d, dv, k, v, f = case[:6]
-    return "%s-%s-dv%d-k%d-v%d-f%d" % (MODEL_NAMES[m], DTYPE_NAMES[d], dv, k, v, f)
+def case_id(r):
+    return "%s-%s-dv%d-k%d-v%d-f%d" % ((MODEL_NAMES[r.model], DTYPE_NAMES[r.dtype]) + key(r)[2:])
 
 
 # (model, dtype, dv, k_max, variant, flags, class, variant_name, fixed_k_ok, fp32_spread)
@@ -540,3 +551,4 @@ CASES = [
 ]
 # END CASES
 CASES_DIGEST = '108d7906a1fec33c'
+RECORDS = [Case(*c) for c in CASES]

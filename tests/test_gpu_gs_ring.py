@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import cgmres_cpp_amd as cg
-from test_gpu_wave import _refs, U_TOL
+from gpu_helpers import U_TOL, _oracle_free_run, _refs
 
 pytestmark = pytest.mark.gpu
 
@@ -30,22 +30,6 @@ def _batch(B, dv, km, tol):
     c = cg.CgmresBatch("pendulum", batch=B, dv=dv, k_max=km, tol=tol, variant=2)
     assert c.variant_name == NAME, (dv, km, B, tol, c.variant_name)
     return c
-
-
-def _oracle_free_run(orc, dv, km, tol, x0, u0, p, ticks, model=0):
-    """x, u after `ticks` closed-loop ticks and the Arnoldi counts / exit reasons of every tick, per instance."""
-    xs, us, counts, reasons = [], [], [], []
-    for i in range(len(x0)):
-        r = orc.Controller(model, dv, km, tol)
-        orc.start_controller(r, x0[i], u0[i], p[i])
-        x, ks, rs = x0[i].copy(), [], []
-        for _ in range(ticks):
-            u = r.control(x)
-            k_o, _, reason_o = r.last_solve()
-            ks.append(k_o), rs.append(reason_o)
-            x = x + r.plant(x, u) * r.dt
-        xs.append(x), us.append(u), counts.append(ks), reasons.append(rs)
-    return np.array(xs), np.array(us), np.array(counts), np.array(reasons)
 
 
 @pytest.mark.parametrize("km", KMAX)

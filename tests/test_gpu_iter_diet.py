@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 import cgmres_cpp_amd as cg
-from test_gpu_gs_ring import _oracle_free_run
+from gpu_helpers import _oracle_free_run
 
 pytestmark = pytest.mark.gpu
 

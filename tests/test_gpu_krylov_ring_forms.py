@@ -24,11 +24,12 @@ import numpy as np
 import pytest
 
 import cgmres_cpp_amd as cg
-from test_gpu_gs_ring import TICKS, _oracle_free_run
+from gpu_helpers import _oracle_free_run
 
 pytestmark = pytest.mark.gpu
 
 B = 20
+TICKS = 12  # as in test_gpu_gs_ring.py: one launch fuses at most 10 ticks, the 11th starts a second launch
 PENDULUM, MSD = 0, 1
 CASES = [(PENDULUM, 20, 2, 13), (PENDULUM, 20, 2, 14),
          (PENDULUM, 20, 3, 1), (PENDULUM, 20, 3, 2), (PENDULUM, 20, 3, 3),

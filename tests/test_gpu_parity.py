@@ -9,41 +9,13 @@ import pytest
 
 import cgmres_cpp_amd as cg
 from conftest import golden_files, golden_ids, load_golden
+from gpu_helpers import DUDT_REL, U_TOL, VARIANTS, new_batch
 
 pytestmark = pytest.mark.gpu
-
-U_TOL = 1e-9
-DUDT_REL = 1e-7
-# 2 = "wg" (default mapping; in fp64 with row-parallel sweeps for the pendulum at 33 <= dv <= 53 — Newton on the trajectory —
-#     and for the semi-active damper at dv <= 53 — scans only; tick_wg.hip.h: NWT),
-# "2s" = the same with FLAG_SERIAL_STATE_SWEEP (the wg kernel with the serial quad sweep, where that differs),
-# 1 = "lane" (reference statement order), 3 = "wg-lean" (two workgroups per CU),
-# 4 = "wave" (one wavefront per controller: the latency mapping; pendulum fp64, dv <= 63, k_max <= 10)
-SERIAL_STATE = "2s"
-VARIANTS = [2, SERIAL_STATE, 1, 3, 4]
-
 
 def dudt_close(a, b, rel=DUDT_REL):
     scale = max(1.0, float(np.max(np.abs(b))))
     return float(np.max(np.abs(a - b))) <= rel * scale
-
-
-def new_batch(*a, **kw):
-    """cg.CgmresBatch; a size / model the wave mapping does not serve skips the test case."""
-    if kw.get("variant") == SERIAL_STATE:
-        model = a[0] if a else kw.get("model")
-        dv = kw.get("dv", 0)
-        row_kernel = (model in (0, "pendulum") and 33 <= dv <= 53) or (model in (2, "semiactive") and dv <= 53)
-        if not row_kernel or kw.get("dtype", "f64") != "f64":
-            pytest.skip("FLAG_SERIAL_STATE_SWEEP only changes the fp64 kernels of the pendulum and the semi-active damper "
-                        "at dim_u*dv <= 160")
-        kw = dict(kw, variant=2, flags=kw.get("flags", 0) | cg.FLAG_SERIAL_STATE_SWEEP)
-    try:
-        return cg.CgmresBatch(*a, **kw)
-    except cg.CgmresHipError as e:
-        if kw.get("variant") == 4 and "wave mapping" in str(e):
-            pytest.skip("the wave mapping does not cover this model / dtype / size")
-        raise
 
 
 def make_batch(case, batch, variant=0, tol=None):

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import cgmres_cpp_amd as cg
-from test_gpu_wave import _refs, _teacher_forced, U_TOL
+from gpu_helpers import U_TOL, _refs, _teacher_forced
 
 pytestmark = pytest.mark.gpu
 

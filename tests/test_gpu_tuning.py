@@ -20,7 +20,7 @@ import pytest
 
 import cgmres_cpp_amd as cg
 import tuning_cases as tc
-from test_gpu_parity import DUDT_REL, U_TOL, VARIANTS, new_batch
+from gpu_helpers import DUDT_REL, U_TOL, VARIANTS, new_batch
 
 pytestmark = pytest.mark.gpu
 

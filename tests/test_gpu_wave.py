@@ -8,46 +8,11 @@ import numpy as np
 import pytest
 
 import cgmres_cpp_amd as cg
+from gpu_helpers import U_TOL, _refs, _teacher_forced
 
 pytestmark = pytest.mark.gpu
 
-U_TOL, DUDT_REL = 1e-9, 1e-7
 WAVE = 4
-
-
-def _refs(orc, model, dv, km, tol, x0, u0, p):
-    out = []
-    for i in range(len(x0)):
-        r = orc.Controller(model, dv, km, tol)
-        orc.start_controller(r, x0[i], u0[i], p[i])
-        out.append(r)
-    return out
-
-
-def _teacher_forced(orc, c, refs, x0, ticks, u_tol=U_TOL):
-    """Every tick: controller state and x taken from the oracle, u / dUdt / counts / exit reasons compared."""
-    x = x0.copy()
-    worst = 0.0
-    for tick in range(ticks):
-        t_o, U_o, d_o = zip(*[r.get_state() for r in refs])
-        c.set_state(t_o[0], np.array(U_o), np.array(d_o))
-        u = c.control(x)
-        n_ax, reason = c.get_status()
-        _, U1, d1 = c.get_state()
-        for i, r in enumerate(refs):
-            ur = r.control(x[i])
-            worst = max(worst, float(np.max(np.abs(u[i] - ur))))
-            # u = U + dUdt*dt (cgmres.hpp:102-109): the bound on u that goes with SURVEY 8(c)'s bound on dUdt — relative to
-            # |u| and to dt*|dUdt| where a time jump makes them large (|dUdt| ~ 1e5 on the two-mass system)
-            d_ref = r.get_state()[2]
-            bound = u_tol * max(1.0, float(np.max(np.abs(ur)))) + r.dt * DUDT_REL * max(1.0, float(np.max(np.abs(d_ref))))
-            assert np.max(np.abs(u[i] - ur)) <= bound, (tick, i, u[i], ur)
-            k_o, _, reason_o = r.last_solve()
-            assert n_ax[i] == k_o and reason[i] == reason_o, (tick, i, n_ax[i], k_o, reason[i], reason_o)
-            d_ref = r.get_state()[2]
-            assert np.max(np.abs(d1[i] - d_ref)) <= DUDT_REL * max(1.0, float(np.max(np.abs(d_ref)))), (tick, i)
-            x[i] = x[i] + r.plant(x[i], ur) * r.dt
-    return worst
 
 
 def test_the_library_takes_the_wave_mapping_for_batches_smaller_than_the_gpu():

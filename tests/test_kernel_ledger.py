@@ -3,9 +3,9 @@ has a case in CASES (which tests/test_gpu_kernel_classes.py runs against the ora
 table says.  A kernel that becomes reachable in plan_wg without a case, and a case that is deleted, both fail here."""
 import pytest
 
+import class_ledger as ledger
 import kernel_classes as kc
 import plan_probe
-from plan_probe import check_layout, config
 
 
 @pytest.fixture(scope="module")
@@ -19,51 +19,11 @@ def members(probe):
 
 
 def test_every_class_of_the_grid_has_a_case_and_no_case_is_outside_it(members):
-    have = {case[6] for case in kc.CASES}
-    print(f"{len(members)} classes over {len(kc.grid())} configurations, {len(kc.CASES)} cases")
-    missing = sorted(set(members) - have)
-    stray = sorted(have - set(members))
-    assert not missing, "classes without a case: " + ", ".join(
-        "%s (%d members, e.g. %s)" % (kc.class_name(c), len(members[c]), kc.case_id(kc.order_a(members[c])[0])) for c in missing)
-    assert not stray, "cases of a class the grid does not yield: " + ", ".join(kc.class_name(c) for c in stray)
-    assert len({case[:6] for case in kc.CASES}) == len(kc.CASES)
+    ledger.assert_every_class_has_a_case(kc, members)
 
 
-def test_the_table_is_the_one_the_admission_tool_wrote():
-    """A guard against an accidental edit (a deleted or changed line), no more: the digest sits in the same file."""
-    assert kc.digest(kc.CASES) == kc.CASES_DIGEST, \
-        "CASES was edited (a case deleted, added or changed) without tools/kernel_case_admission.py --select --write"
-
-
-def test_every_case_resolves_to_its_recorded_class_and_name(probe):
-    """... at the grid's batch and at the batches and tolerances the GPU test creates its handles with, on a small and a
-    large device: the class recorded is the kernel launched there (the GPU test itself can only ask for variant_name)."""
-    bad = []
-    for case in kc.CASES:
-        m, d, dv, k, v, f = case[:6]
-        for batch in (kc.BATCH, 20, 11):
-            for tol in (kc.TOL, 0.0):
-                for cus in (kc.CUS, 8):
-                    r, _ = plan_probe.plan(probe, config(m, d, dv, k, batch, v, f, tol), cus)
-                    got = None if r is None else (kc.class_of(dict(r, model=m, dtype=d)), r["variant_name"])
-                    if got != (case[6], case[7]):
-                        bad.append((kc.case_id(case), batch, tol, cus, got, case[6:8]))
-    assert not bad, bad[:5]
-
-
-def test_the_allocation_of_every_case_covers_its_layout(probe):
-    """check_layout (tests/plan_probe.py) at the batch sizes the GPU test runs: before any of these shapes reaches a GPU."""
-    bad = []
-    for case in kc.CASES:
-        m, d, dv, k, v, f = case[:6]
-        for batch in (kc.BATCH, 20, 11):
-            cfg = config(m, d, dv, k, batch, v, f, kc.TOL)
-            r, why = plan_probe.plan(probe, cfg, kc.CUS)
-            assert r is not None, (kc.case_id(case), why)
-            problems = check_layout(probe, cfg, r)
-            if problems:
-                bad.append((kc.case_id(case), batch, problems))
-    assert not bad, bad[:5]
+(test_the_table_is_the_one_the_admission_tool_wrote, test_every_case_resolves_to_its_recorded_class_and_name,
+ test_the_allocation_of_every_case_covers_its_layout) = ledger.table_tests(kc, "tools/kernel_case_admission.py")
 
 
 def test_every_class_has_a_case_usable_with_the_reference_tolerance():
@@ -71,17 +31,18 @@ def test_every_class_has_a_case_usable_with_the_reference_tolerance():
     its class.  That a case is usable with tol = 1e-6 is what tools/kernel_case_admission.py measures when it writes the
     table and re-measures in its check mode; nothing here repeats that."""
     per_class = {}
-    for case in kc.CASES:
-        m, d, dv, k, v, f, cls, name, fixed_k_ok, spread = case
-        assert cls[:2] == (m, d) and isinstance(fixed_k_ok, bool) and isinstance(name, str)
-        assert v in kc.VARIANTS and f in kc.FLAGS and dv in kc.DV and k in kc.KMAX
-        assert (dv, k) not in kc.DEVICE_MISSES.get(cls, {})
-        if d == 0:
+    for case in kc.RECORDS:
+        cls, spread = case.cls, case.fp32_spread
+        assert (kc.model_of(cls), kc.dtype_of(cls)) == (case.model, case.dtype)
+        assert isinstance(case.fixed_k_ok, bool) and isinstance(case.variant_name, str)
+        assert case.variant in kc.VARIANTS and case.flags in kc.FLAGS and case.dv in kc.DV and case.k_max in kc.KMAX
+        assert (case.dv, case.k_max) not in kc.DEVICE_MISSES.get(cls, {})
+        if case.dtype == 0:
             assert spread is None
         elif spread is not None:
             assert len(spread) == 2 and any(spread)
             for mode in spread:
                 assert mode is None or (len(mode) == 3 and any(mode) and all(s is None or s > 0 for s in mode))
-            assert fixed_k_ok or spread[1] is None
+            assert case.fixed_k_ok or spread[1] is None
         per_class.setdefault(cls, []).append(case)
     assert all(1 <= len(v) <= 2 for v in per_class.values())

@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 
+import class_ledger as ledger
 import plan_probe
 import user_kernel_classes as uk
 from plan_probe import check_layout, config
@@ -56,73 +57,29 @@ def test_the_aliases_have_the_shapes_they_are_there_for(probe):
 
 
 def test_every_class_of_the_grid_has_a_case_and_no_case_is_outside_it(members):
-    have = {case[5] for case in uk.CASES}
-    print(f"{len(members)} classes over {len(uk.grid())} configurations (+ the lane members), {len(uk.CASES)} cases")
-    missing = sorted(set(members) - have)
-    stray = sorted(have - set(members))
-    assert not missing, "classes without a case: " + ", ".join("%s (%d members)" % (uk.class_name(c), len(members[c])) for c in missing)
-    assert not stray, "cases of a class the grid does not yield: " + ", ".join(uk.class_name(c) for c in stray)
-    assert len({case[:5] for case in uk.CASES}) == len(uk.CASES)
+    ledger.assert_every_class_has_a_case(uk, members, " (+ the lane members)")
     # one wave and one lane class per alias where the wave mapping fits, wg classes for all five
     for a in range(len(uk.ALIASES)):
-        kinds = {uk.kind(c) for c in members if c[0] == a}
+        kinds = {uk.kind(c) for c in members if uk.alias_of(c) == a}
         assert kinds == ({"wg", "wave", "lane"} if uk.ALIASES[a] != "Shape521" else {"wg", "lane"}), (a, kinds)
 
 
-def test_the_table_is_the_one_the_admission_tool_wrote():
-    """A guard against an accidental edit (a deleted or changed line), no more: the digest sits in the same file."""
-    assert uk.digest(uk.CASES) == uk.CASES_DIGEST, \
-        "CASES was edited (a case deleted, added or changed) without tools/user_case_admission.py --select --write"
-
-
-def test_every_case_resolves_to_its_recorded_class_and_name(probe):
-    """... at the grid's batch and at the batches and tolerances the GPU test creates its handles with, on a small and a
-    large device: the class recorded is the kernel launched there (the GPU test itself can only ask for variant_name)."""
-    bad = []
-    for case in uk.CASES:
-        a, dv, k, v, f, cls, name = case[:7]
-        if uk.kind(cls) == "lane":
-            assert (v, f, name) == (1, 0, "lane")
-            continue
-        for batch in (uk.BATCH, 20, 11):
-            for tol in (uk.TOL, 0.0):
-                for cus in (uk.CUS, 8):
-                    r = uk.resolve(probe, a, dv, k, v, f, batch, tol, cus)
-                    got = None if r is None else (uk.class_of(a, r), r["variant_name"])
-                    if got != (cls, name):
-                        bad.append((uk.case_id(case), batch, tol, cus, got, (cls, name)))
-    assert not bad, bad[:5]
-
-
-def test_the_allocation_of_every_case_covers_its_layout(probe):
-    """check_layout (tests/plan_probe.py), the look-ahead rule included, at the batch sizes the GPU test runs: before any of
-    these shapes reaches a GPU.  (A wave case: the wg context of its sizes, which the handle keeps for the hooks.)"""
-    bad = []
-    for case in uk.CASES:
-        a, dv, k, v, f, cls = case[:6]
-        if uk.kind(cls) == "lane":
-            continue
-        for batch in (uk.BATCH, 20, 11):
-            cfg = config(a, 0, dv, k, batch, v, f, uk.TOL)
-            r, why = plan_probe.plan(probe, cfg, uk.CUS)
-            assert r is not None, (uk.case_id(case), why)
-            problems = check_layout(probe, cfg, r)
-            if problems:
-                bad.append((uk.case_id(case), batch, problems))
-    assert not bad, bad[:5]
+(test_the_table_is_the_one_the_admission_tool_wrote, test_every_case_resolves_to_its_recorded_class_and_name,
+ test_the_allocation_of_every_case_covers_its_layout) = ledger.table_tests(uk, "tools/user_case_admission.py")
 
 
 def test_shape_of_the_table():
     per_class = {}
-    for case in uk.CASES:
-        a, dv, k, v, f, cls, name, fixed_k_ok, member = case
-        assert cls[0] == a and isinstance(fixed_k_ok, bool) and isinstance(name, str) and member and set(member) <= set("ABN")
-        assert v in uk.VARIANTS + (1,) and f in uk.FLAGS and dv in uk.DV and k in uk.KMAX
-        assert (dv, k) not in uk.DEVICE_MISSES.get(cls, {})
+    for case in uk.RECORDS:
+        cls = case.cls
+        assert uk.alias_of(cls) == case.alias and isinstance(case.fixed_k_ok, bool) and isinstance(case.variant_name, str)
+        assert case.member and set(case.member) <= set("ABN")
+        assert case.variant in uk.VARIANTS + (1,) and case.flags in uk.FLAGS and case.dv in uk.DV and case.k_max in uk.KMAX
+        assert (case.dv, case.k_max) not in uk.DEVICE_MISSES.get(cls, {})
         per_class.setdefault(cls, []).append(case)
     for cls, cases in per_class.items():
         assert 1 <= len(cases) <= len(uk.orders(cls)), uk.class_name(cls)
-        assert sorted("".join(c[8] for c in cases)) == sorted(w for w, _ in uk.orders(cls)), uk.class_name(cls)
+        assert sorted("".join(c.member for c in cases)) == sorted(w for w, _ in uk.orders(cls)), uk.class_name(cls)
     for cls, misses in uk.DEVICE_MISSES.items():
         assert len(misses) <= 1 and cls in per_class, uk.class_name(cls)
 

@@ -20,17 +20,18 @@ The lane class's members are every (dv, k_max) of the grid on variant 1.
 CASES, chosen by tools/user_case_admission.py --select from the ADMITTED members (measured on the reference side, the
 fp64 rule of tools/kernel_case_admission.py unchanged: the tool's docstring has it):
 
-    wg classes   A and B by kernel_classes.order_a / order_b (A: smallest dv with k_max >= 3; B: largest lds_bytes)
+    wg classes   A and B by class_ledger.order_a / order_b (A: smallest dv with k_max >= 3; B: largest lds_bytes)
     wave class   A, B' (largest dv, there the largest k_max: dv 63, k_max 10) and N: the admitted dv nearest to 17 with
                  k_max 5 (dv 17 puts one stage past a 16-lane DPP row; Chain4 covers the other row edges)
     lane class   A only
 
 DEVICE_MISSES as in tests/kernel_classes.py (empty: nothing has been moved there).  tests/test_user_kernel_ledger.py is
 the CPU side."""
-import hashlib
+from collections import namedtuple
+from operator import itemgetter
 
-from kernel_classes import order_a, order_b
-from plan_probe import alias_info, config, plan
+import plan_probe
+from class_ledger import CASE_COLUMNS, MEMBER_COLUMNS, order_a, order_b
 
 ALIASES = ("Shape110", "Shape321", "Shape262", "Shape431", "Shape521")
 FLAG_BITS = {"SERIAL_COSTATE": 1, "IPW8": 2, "TWO_PASS_COSTATE": 8}
@@ -48,15 +49,27 @@ DEVICE_MISSES = {}
 REFUSED_WG = (3, 5, 5)
 
 
+# one row of CASES; one configuration of grid() (or of the lane kernel) with what the planner makes of it
+Case = namedtuple("Case", "alias " + CASE_COLUMNS + " member")
+Member = namedtuple("Member", "alias " + MEMBER_COLUMNS)
+
+
+def cfg(alias, dv, k_max, variant, flags, batch=BATCH, tol=TOL):
+    return plan_probe.config(alias, 0, dv, k_max, batch, variant, flags, tol)
+
+
 def resolve(lib, alias, dv, k_max, variant, flags, batch=BATCH, tol=TOL, cus=CUS):
-    """The planner's result for one configuration (variant 2, 3, 4 or 0), or None where it refuses."""
-    return plan(lib, config(alias, 0, dv, k_max, batch, variant, flags, tol), cus)[0]
+    """The planner's result for one configuration (variant 2, 3, 4 or 0, with its alias), or None where it refuses."""
+    r, _ = plan_probe.plan(lib, cfg(alias, dv, k_max, variant, flags, batch, tol), cus)
+    if r is not None:
+        r["alias"] = alias
+    return r
 
 
-def class_of(alias, r):
+def class_of(r):
     if r["wave"]:
-        return wave_class(alias)
-    return (alias, r["ipw"], r["maxm"], r["par"], r["plan"], r["cs_chunks"])
+        return wave_class(r["alias"])
+    return (r["alias"], r["ipw"], r["maxm"], r["par"], r["plan"], r["cs_chunks"])
 
 
 def wave_class(alias):
@@ -67,8 +80,12 @@ def lane_class(alias):
     return (alias, 0, 0, 0, 0, 0)
 
 
+# the fields of a class, by name
+alias_of, ipw, maxm, par, plan, cs_chunks = (itemgetter(i) for i in range(6))
+
+
 def kind(c):
-    return {0: "lane", 1: "wave"}.get(c[1], "wg")
+    return {0: "lane", 1: "wave"}.get(ipw(c), "wg")
 
 
 def class_name(c):
@@ -82,26 +99,25 @@ def grid():
 
 
 def members(lib):
-    """class -> its members, in the row layout kernel_classes.order_a / order_b sort:
-    (alias, 0, dv, k_max, variant, flags, lds_bytes, variant_name)"""
+    """class -> its members"""
     out = {}
-    for a, dv, k, v, f in grid():
-        r = resolve(lib, a, dv, k, v, f)
+    for row in grid():
+        r = resolve(lib, *row)
         if r is not None:
-            out.setdefault(class_of(a, r), []).append((a, 0, dv, k, v, f, r["lds_bytes_tick"], r["variant_name"]))
+            out.setdefault(class_of(r), []).append(Member(*row, r["lds_bytes_tick"], r["variant_name"]))
     for a in range(len(ALIASES)):
-        out[lane_class(a)] = [(a, 0, dv, k, 1, 0, 0, "lane") for dv in DV for k in KMAX]
+        out[lane_class(a)] = [Member(a, dv, k, 1, 0, 0, "lane") for dv in DV for k in KMAX]
     return out
 
 
 def order_wave_b(rows):
     """largest dv, there the largest k_max; the plain configuration first"""
-    return sorted(rows, key=lambda r: (-r[2], -r[3], r[5]))
+    return sorted(rows, key=lambda r: (-r.dv, -r.k_max, r.flags))
 
 
 def order_wave_near(rows):
     """k_max 5, by the distance of dv from 17 (the shorter horizon first at equal distance)"""
-    return sorted((r for r in rows if r[3] == WAVE_NEAR_K), key=lambda r: (abs(r[2] - WAVE_NEAR_DV), r[2], r[5]))
+    return sorted((r for r in rows if r.k_max == WAVE_NEAR_K), key=lambda r: (abs(r.dv - WAVE_NEAR_DV), r.dv, r.flags))
 
 
 def orders(c):
@@ -113,19 +129,17 @@ def orders(c):
     return (("A", order_a), ("B", order_b))
 
 
-def digest(cases):
-    """of the whole table, columns included: CASES_DIGEST is written with the table, so a case that is deleted or edited
-    by hand shows in tests/test_user_kernel_ledger.py"""
-    return hashlib.sha256(repr(sorted(cases)).encode()).hexdigest()[:16]
+def key(r):
+    """the configuration of a case or a member"""
+    return (r.alias, r.dv, r.k_max, r.variant, r.flags)
 
 
-def case_id(case):
-    a, dv, k, v, f = case[:5]
-    return "%s-dv%d-k%d-v%d-f%d" % (ALIASES[a], dv, k, v, f)
+def case_id(r):
+    return "%s-dv%d-k%d-v%d-f%d" % ((ALIASES[r.alias],) + key(r)[1:])
 
 
 def dims(lib, alias):
-    return alias_info(lib, alias)
+    return plan_probe.alias_info(lib, alias)
 
 
 # (alias, dv, k_max, variant, flags, class, variant_name, fixed_k_ok, member)
@@ -277,3 +291,4 @@ CASES = [
 ]
 # END CASES
 CASES_DIGEST = 'a45431abacdde86f'
+RECORDS = [Case(*c) for c in CASES]

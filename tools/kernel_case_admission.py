@@ -29,7 +29,8 @@ Admitted for a tolerance mode:
 A candidate that is not admitted with tol = 1e-6 is passed over for the next member of its class in the same ordering;
 one that is admitted with tol = 1e-6 only gets fixed_k_ok = False.  kernel_classes.DEVICE_MISSES lists the shapes that were
 admitted here and that a kernel then missed on the device with the lane mapping inside its bounds: findings about that
-kernel, passed over in the same way and named in the table."""
+kernel, passed over in the same way and named in the table.  The selection, the check loop and the fp64 rule are those
+of tests/class_ledger.py, which tools/user_case_admission.py uses as well."""
 import math
 import os
 import shutil
@@ -42,13 +43,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+import class_ledger as ledger  # noqa: E402
 import kernel_classes as kc  # noqa: E402
 import plan_probe  # noqa: E402
+from class_ledger import LOOP_TICKS, N_INST, N_TICKS, TOLS, worse  # noqa: E402
 from oracle import orc  # noqa: E402
 
-N_INST, N_TICKS, LOOP_TICKS = 20, 6, 12
-TOLS = (1e-6, 0.0)
-F64_U, F64_D, F64_LOOP = 1e-10, 1e-8, 1e-8
 F32_U, F32_D, F32_LOOP, F32_LOOP_D = 1e-4 / 8, 5e-3 / 8, 1e-4 / 8, 2e-3 / 8
 PLAIN, FAST = "-ffp-contract=off", "-ffp-contract=fast -mfma"
 
@@ -75,10 +75,6 @@ def build_fast_flavour():
     subprocess.run(["make", "-C", tmp, "oracle", "CXXFLAGS=" + fast_flags()], check=True, stdout=subprocess.DEVNULL)
     orc.register_library("fast", os.path.join(tmp, "liboracle.so"))
     return tmp
-
-
-def worse(a, b):
-    return max(a, b) if math.isfinite(b) else math.inf  # (max() drops a NaN)
 
 
 def measure(model, dtype, dv, k_max, tol):
@@ -148,9 +144,9 @@ def measure_loop(model, dtype, dv, k_max, tol):
 _cache = {}
 
 
-def admission(model, dtype, dv, k_max):
-    """per tolerance mode: (admitted, figures, fp32 spread triple or None)"""
-    key = (model, dtype, dv, k_max)
+def admission(r):
+    """per tolerance mode: (admitted, figures, fp32 spread triple or None) of the shape of a case or member"""
+    key = model, dtype, dv, k_max = (r.model, r.dtype, r.dv, r.k_max)
     if key not in _cache:
         out = []
         for tol in TOLS:
@@ -158,7 +154,7 @@ def admission(model, dtype, dv, k_max):
             sl, sld, agree_l, full = measure_loop(model, dtype, dv, k_max, tol)
             finite = all(math.isfinite(v) for v in (su, sU, sd, sl, sld))
             if dtype == 0:
-                ok = finite and agree and su <= F64_U and sd <= F64_D and agree_l and sl <= F64_LOOP and (tol > 0 or full)
+                ok = finite and ledger.f64_admitted(tol, su, sd, agree, sl, agree_l, full)
                 spread = None
             else:
                 ok = finite and sl <= F32_LOOP and sld <= F32_LOOP_D
@@ -181,73 +177,18 @@ def columns(adm):
     return adm[1][0], (spread if any(spread) else None)
 
 
-def pick(rows, cls):
-    """the first member of `rows` admitted with tol = 1e-6 and not among the device misses of class `cls`, and one line per
-    horizon passed over on the way (its k_max values and the figures of the first of them)"""
-    passed = {}
-    for r in rows:
-        adm = admission(*r[:4])
-        miss = kc.DEVICE_MISSES.get(cls, {}).get(r[2:4])
-        if adm[0][0] and not miss:
-            break
-        what = "DEVICE MISS, " + miss + "; reference side" if miss else "not admitted"
-        ks = passed.setdefault((r[2], what), ([], figures(adm)))[0]
-        if r[3] not in ks:
-            ks.append(r[3])
-    else:
-        r = adm = None
-    text = ["dv %d k_max %s %s (k_max %d: %s)" % (dv, ",".join(map(str, ks)), what, ks[0], fig) for (dv, what), (ks, fig) in passed.items()]
-    return r, adm, text
+def row(c, r, adm, letters, n_members):
+    return ["    # %s of %d, lds_bytes %d: %s" % (letters, n_members, r.lds_bytes, figures(adm)),
+            "    (%d, %d, %d, %d, %d, %d, %r, %r, %r, %r)," % (kc.key(r) + (c, r.variant_name) + columns(adm))]
+
+
+def label(c, r, which, rows):
+    """"A = B" where the member of both selections is also the first of order_b before admission"""
+    return "A = B" if which == ["A", "B"] and ledger.order_b(rows)[0] == r else which[0]
 
 
 def select():
-    lib = plan_probe.probe()
-    mem = kc.members(lib)
-    lines = ["CASES = ["]
-    for c in sorted(mem):
-        chosen = []
-        for which, order in (("A", kc.order_a), ("B", kc.order_b)):
-            r, adm, passed = pick(order(mem[c]), c)
-            if r is None:
-                lines.append("    # %s: NO MEMBER ADMITTED" % kc.class_name(c))
-                lines += ["    #   " + t for t in passed[:6]]
-                break
-            if chosen and chosen[0][0][:6] == r[:6]:
-                continue
-            chosen.append((r, adm, passed, which))
-        if len(chosen) == 1 and chosen[0][3] == "A" and kc.order_b(mem[c])[0][:6] == chosen[0][0][:6]:
-            chosen[0] = chosen[0][:3] + ("A = B",)
-        for r, adm, passed, which in chosen:
-            lines += ["    # " + t for t in passed]
-            lines.append("    # %s of %d, lds_bytes %d: %s" % (which, len(mem[c]), r[6], figures(adm)))
-            fixed_k_ok, spread = columns(adm)
-            lines.append("    (%d, %d, %d, %d, %d, %d, %r, %r, %r, %r)," % (r[:6] + (c, r[7], fixed_k_ok, spread)))
-    lines.append("]")
-    return "\n".join(lines)
-
-
-def write_block(text):
-    """the CASES block of tests/kernel_classes.py and the digest behind it"""
-    path = os.path.join(ROOT, "tests", "kernel_classes.py")
-    src = open(path).read()
-    head, rest = src.split("# BEGIN CASES", 1)
-    first, tail = rest.split("\n", 1)[0], rest.split("# END CASES\n", 1)[1]
-    tail = tail.split("\n", 1)[1]  # (the CASES_DIGEST line)
-    scope = {}
-    exec(text, scope)
-    open(path, "w").write(head + "# BEGIN CASES" + first + "\n" + text + "\n# END CASES\nCASES_DIGEST = %r\n" % kc.digest(scope["CASES"]) + tail)
-
-
-def check():
-    """re-measure CASES; 0 when every recorded column is reproduced"""
-    bad = 0
-    for case in kc.CASES:
-        adm = admission(*case[:4])
-        ok = adm[0][0] and columns(adm) == (case[8], case[9]) and case[2:4] not in kc.DEVICE_MISSES.get(case[6], {})
-        bad += not ok
-        print("%-40s %s  %s" % (kc.case_id(case), figures(adm), "ok" if ok else "RECORDED %r, MEASURED %r" % (case[8:10], columns(adm))))
-    print("%d cases, %d not reproduced" % (len(kc.CASES), bad))
-    return 1 if bad else 0
+    return ledger.select(kc, kc.members(plan_probe.probe()), admission, figures, row, label)
 
 
 def main(argv):
@@ -257,14 +198,14 @@ def main(argv):
             text = select()
             print(text)
             if "--write" in argv:
-                write_block(text)
+                ledger.write_block(os.path.join(ROOT, "tests", "kernel_classes.py"), text)
             return 0
         if len(argv) == 4:
-            m, d, dv, k = (int(a) for a in argv)
-            adm = admission(m, d, dv, k)
-            print(kc.case_id((m, d, dv, k, 2, 0)), figures(adm), "admitted:", [a[0] for a in adm], "fp32_spread:", [a[2] for a in adm])
+            r = kc.Member(*(int(a) for a in argv), 2, 0, 0, "")
+            adm = admission(r)
+            print(kc.case_id(r), figures(adm), "admitted:", [a[0] for a in adm], "fp32_spread:", [a[2] for a in adm])
             return 0
-        return check()
+        return ledger.check(kc, admission, figures, columns, lambda case: (case.fixed_k_ok, case.fp32_spread), 40)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 

@@ -1,5 +1,6 @@
 """Which shapes of tests/user_kernel_classes.py can hold a plugin kernel to the oracle at all: measured on the reference
-side, on the CPU, without a GPU.  The fp64 rule of tools/kernel_case_admission.py, unchanged, for user models.
+side, on the CPU, without a GPU.  The fp64 rule of tools/kernel_case_admission.py (tests/class_ledger.py has it, with
+the selection and the check loop, for both tools), for user models.
 
     python tools/user_case_admission.py            # re-measure every case of CASES and compare with its recorded columns
     python tools/user_case_admission.py --select   # choose the members of every class; print the CASES block
@@ -28,13 +29,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+import class_ledger as ledger  # noqa: E402
 import plan_probe  # noqa: E402
 import user_kernel_classes as uk  # noqa: E402
 import user_oracle  # noqa: E402
-
-N_INST, N_TICKS, LOOP_TICKS = 20, 6, 12
-TOLS = (1e-6, 0.0)
-F64_U, F64_D, F64_LOOP = 1e-10, 1e-8, 1e-8
+from class_ledger import LOOP_TICKS, N_INST, N_TICKS, TOLS  # noqa: E402
 
 _tmp = None
 _dims = {}
@@ -45,10 +44,6 @@ def exes(alias):
     cls = uk.ALIASES[alias]
     return tuple(user_oracle.build(plan_probe.USER_MODELS_HPP, cls, os.path.join(_tmp, f"{cls}_{name}"), flavour)
                  for name, flavour in (("plain", user_oracle.PLAIN), ("fast", user_oracle.FAST)))
-
-
-def worse(a, b):
-    return max(a, b) if math.isfinite(b) else math.inf  # (max() drops a NaN)
 
 
 def rel_rows(a, b):
@@ -88,17 +83,15 @@ def measure_loop(alias, dv, k_max, tol):
 _cache = {}
 
 
-def admission(alias, dv, k_max):
-    """per tolerance mode: (admitted, figures)"""
-    key = (alias, dv, k_max)
+def admission(r):
+    """per tolerance mode: (admitted, figures) of the shape of a case or member"""
+    key = alias, dv, k_max = (r.alias, r.dv, r.k_max)
     if key not in _cache:
         out = []
         for tol in TOLS:
             su, sd, agree = measure(alias, dv, k_max, tol)
             sl, agree_l, full = measure_loop(alias, dv, k_max, tol)
-            finite = all(math.isfinite(v) for v in (su, sd, sl))
-            ok = finite and agree and su <= F64_U and sd <= F64_D and agree_l and sl <= F64_LOOP and (tol > 0 or full)
-            out.append((ok, (su, sd, agree, sl, agree_l, full)))
+            out.append((ledger.f64_admitted(tol, su, sd, agree, sl, agree_l, full), (su, sd, agree, sl, agree_l, full)))
         _cache[key] = out
     return _cache[key]
 
@@ -109,72 +102,17 @@ def figures(adm):
                       for _, f in adm)
 
 
-def pick(rows, cls):
-    """the first member of `rows` admitted with tol = 1e-6 and not among the device misses of class `cls`, and one line per
-    horizon passed over on the way (its k_max values and the figures of the first of them)"""
-    passed = {}
-    for r in rows:
-        adm = admission(r[0], r[2], r[3])
-        miss = uk.DEVICE_MISSES.get(cls, {}).get(r[2:4])
-        if adm[0][0] and not miss:
-            break
-        what = "DEVICE MISS, " + miss + "; reference side" if miss else "not admitted"
-        ks = passed.setdefault((r[2], what), ([], figures(adm)))[0]
-        if r[3] not in ks:
-            ks.append(r[3])
-    else:
-        r = adm = None
-    text = ["dv %d k_max %s %s (k_max %d: %s)" % (dv, ",".join(map(str, ks)), what, ks[0], fig) for (dv, what), (ks, fig) in passed.items()]
-    return r, adm, text
+def fixed_k_ok(adm):
+    return adm[1][0]
+
+
+def row(c, r, adm, letters, n_members):
+    return ["    # %s: %s of %d, lds_bytes %d: %s" % (uk.class_name(c), letters, n_members, r.lds_bytes, figures(adm)),
+            "    (%d, %d, %d, %d, %d, %r, %r, %r, %r)," % (uk.key(r) + (c, r.variant_name, fixed_k_ok(adm), letters))]
 
 
 def select():
-    lib = plan_probe.probe_user()
-    mem = uk.members(lib)
-    lines = ["CASES = ["]
-    for c in sorted(mem):
-        chosen = []  # [row, adm, passed, letters]
-        for which, order in uk.orders(c):
-            r, adm, passed = pick(order(mem[c]), c)
-            if r is None:
-                lines.append("    # %s %s: NO MEMBER ADMITTED" % (uk.class_name(c), which))
-                lines += ["    #   " + t for t in passed[:6]]
-                continue
-            same = [ch for ch in chosen if ch[0][:6] == r[:6]]
-            if same:
-                same[0][3] += which
-            else:
-                chosen.append([r, adm, passed, which])
-        for r, adm, passed, which in chosen:
-            lines += ["    # " + t for t in passed]
-            lines.append("    # %s: %s of %d, lds_bytes %d: %s" % (uk.class_name(c), which, len(mem[c]), r[6], figures(adm)))
-            lines.append("    (%d, %d, %d, %d, %d, %r, %r, %r, %r)," % (r[0], r[2], r[3], r[4], r[5], c, r[7], adm[1][0], which))
-    lines.append("]")
-    return "\n".join(lines)
-
-
-def write_block(text):
-    """the CASES block of tests/user_kernel_classes.py and the digest behind it"""
-    path = os.path.join(ROOT, "tests", "user_kernel_classes.py")
-    src = open(path).read()
-    head, rest = src.split("# BEGIN CASES", 1)
-    first, tail = rest.split("\n", 1)[0], rest.split("# END CASES\n", 1)[1]
-    tail = tail.split("\n", 1)[1]  # (the CASES_DIGEST line)
-    scope = {}
-    exec(text, scope)
-    open(path, "w").write(head + "# BEGIN CASES" + first + "\n" + text + "\n# END CASES\nCASES_DIGEST = %r\n" % uk.digest(scope["CASES"]) + tail)
-
-
-def check():
-    """re-measure CASES; 0 when every recorded column is reproduced"""
-    bad = 0
-    for case in uk.CASES:
-        adm = admission(case[0], case[1], case[2])
-        ok = adm[0][0] and adm[1][0] == case[7] and case[1:3] not in uk.DEVICE_MISSES.get(case[5], {})
-        bad += not ok
-        print("%-28s %s  %s" % (uk.case_id(case), figures(adm), "ok" if ok else "RECORDED %r, MEASURED %r" % (case[7], adm[1][0])))
-    print("%d cases, %d not reproduced" % (len(uk.CASES), bad))
-    return 1 if bad else 0
+    return ledger.select(uk, uk.members(plan_probe.probe_user()), admission, figures, row, lambda c, r, which, rows: "".join(which))
 
 
 def main(argv):
@@ -190,14 +128,14 @@ def main(argv):
             text = select()
             print(text)
             if "--write" in argv:
-                write_block(text)
+                ledger.write_block(os.path.join(ROOT, "tests", "user_kernel_classes.py"), text)
             return 0
         if len(argv) == 3:
-            a, dv, k = (int(v) for v in argv)
-            adm = admission(a, dv, k)
-            print(uk.case_id((a, dv, k, 2, 0)), figures(adm), "admitted:", [x[0] for x in adm])
+            r = uk.Member(*(int(v) for v in argv), 2, 0, 0, "")
+            adm = admission(r)
+            print(uk.case_id(r), figures(adm), "admitted:", [x[0] for x in adm])
             return 0
-        return check()
+        return ledger.check(uk, admission, figures, fixed_k_ok, lambda case: case.fixed_k_ok, 28)
     finally:
         shutil.rmtree(_tmp, ignore_errors=True)
 
