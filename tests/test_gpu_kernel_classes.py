@@ -12,13 +12,26 @@ one; the seeded start of orc.batch_scenario.  Per case, with tol = 1e-6 and, whe
   * 12 ticks of closed_loop_device from the same start (one launch boundary: the class's hand-over through HBM) against
     the oracle's free run.  fp64: the bounds of test_gpu_gs_ring.py (x and u within 1e-7, the last tick's counts and
     reasons equal); fp32: the bounds of test_gpu_closed_loop.test_closed_loop_device_vs_oracle.
+  * the same 12 ticks under the loop's per-tick inputs, which every instantiation of tick_wg_kernel consumes in its own
+    code (the parameter table in LDS or, on the lean plan, in HBM; y_0 = x_0 + v_0 of every launch; the plant block's u
+    from registers, LDS or HBM; 8 or 16 instances per workgroup), as per-instance device buffers of seeded sequences
+    (class_harness.loop_inputs), in two legs: "ptau", a reference that moves with the tick and along the horizon
+    (closed_loop_device_ptau; pendulum and msd), and "all", that with a process disturbance d and a measurement noise v
+    (closed_loop_device_ex).  Behind the loop one plain control() of the x it left: the handle keeps the last tick's
+    horizon and drops d and v.  Against the oracle driven tick by tick with the three statements of
+    include/cgmres_hip.h (inputs_reference).  fp64: u, x and the follow-up u within 1e-7, the last tick's counts and
+    reasons equal, with tol = 0 k_max natural exits, |t - 12 dt| <= 1e-12; fp32: u, x and the follow-up u within 1e-4
+    (U and dUdt are not compared: under this noise the two oracle builds differ by up to 4.7e-3 relative on dUdt).
+    The "all" leg skips msd in fp32, where the two oracle builds themselves end 4.6e-5 to 2.4e-4 apart
+    (kernel_classes.leg_skip and the figures above it; tools/kernel_case_admission.py --inputs measures them).  What a
+    wrong index costs, and what fp32 can and cannot see of it: tests/test_class_harness.py, planted faults.
 
 An fp64 case that exceeds a bound is run again on variant 1, the lane mapping, which keeps the reference's statement
 order: where that fails as well the shape is ill-conditioned and tools/kernel_case_admission.py let it through (mend its
 rule, replace the case); where the lane mapping passes, the kernel is wrong.  The failure message says which.
 
-The comparison, the driver and the two test bodies are those of tests/class_harness.py, shared with
-tests/test_gpu_user_kernel_classes.py.  Each check prints its worst |du| and |ddUdt| as a fraction of the bound before it
+The comparisons, the drivers and the test bodies are those of tests/class_harness.py, the first two bodies shared with
+tests/test_gpu_user_kernel_classes.py (whose oracle is an executable with fixed forms: no sequences there).  Each check prints its worst |du| and |ddUdt| as a fraction of the bound before it
 asserts."""
 import numpy as np
 import pytest
@@ -66,6 +79,20 @@ def reference(orc, case, tol):
     return _refs[key]
 
 
+def inputs_reference(orc, case, tol, leg):
+    """harness.oracle_loop_inputs of the B16 seeded instances under the leg's sequences of harness.loop_inputs (fp32:
+    cast to float32 once, the oracle reads the cast values).  Computed once per shape, tolerance and leg, never modified."""
+    key = (case.model, case.dtype, case.dv, case.k_max, tol, leg)
+    if key not in _refs:
+        x0, u0, p = orc.batch_scenario(case.model, B16)
+        dims = orc.Controller(case.model, case.dv, case.k_max)
+        npdt = np.float32 if case.dtype == 1 else np.float64
+        seq, d, v = harness.leg_of(leg, *harness.loop_inputs((dims.dim_x, dims.dim_p), case.dv, p, npdt))
+        _refs[key] = harness.oracle_loop_inputs(orc, case.model, kc.DTYPE_NAMES[case.dtype], case.dv, case.k_max, tol,
+                                                x0, u0, p, seq, d, v)
+    return _refs[key]
+
+
 def batch_of(case, tol, variant=None):
     B = B16 if kc.ipw(case.cls) == 16 else B8
     kw = dict(batch=B, dv=case.dv, k_max=case.k_max, tol=tol, dtype=kc.DTYPE_NAMES[case.dtype])
@@ -88,5 +115,7 @@ def bounds(case, tol):
 
 
 SIDE = harness.Side(kc, "kernel class", "orc", reference, batch_of, scenario, bounds,
-                    "loop: |du|,|dx|/bound {wu:.3g} |ddUdt|/bound {wd:.3g}")
+                    "loop: |du|,|dx|/bound {wu:.3g} |ddUdt|/bound {wd:.3g}", inputs_reference)
 test_teacher_forced_ticks_vs_oracle, test_device_loop_across_a_launch_boundary_vs_oracle = harness.class_tests(SIDE, cg)
+(test_device_loop_with_a_moving_reference_vs_oracle,
+ test_device_loop_with_disturbance_noise_and_moving_reference_vs_oracle) = harness.class_inputs_tests(SIDE, cg)

@@ -1,13 +1,19 @@
 """GPU parity of the WAVE mapping (variant 4, csrc/tick_wave.hip.h: one wavefront per controller, the horizon
 recurrences of cgmres.hpp:132-153 as DPP wave scans, Newton's method on the nonlinear part of the trajectory) beyond
 what the variant-parametrised tests of test_gpu_parity.py / test_gpu_closed_loop.py cover: its own fall-back paths,
-every exit of gmres.hpp on the pendulum, the exported Krylov arrays, horizon lengths at the edges of the lane mapping,
-and how the library picks the mapping.  Checker: the oracle (oracle/liboracle.so), same seeded inputs.
-Tolerances are SURVEY.md §8(c)'s (fp64 teacher-forced: |du| <= 1e-9, |dUdt| <= 1e-7 rel, Arnoldi counts equal)."""
+every exit of gmres.hpp on the pendulum, the exported Krylov arrays, horizon lengths at the edges of the lane mapping
+(teacher-forced, and the fused loop under a moving reference, a disturbance and a measurement noise: the horizon is
+spread over the lanes, so a per-tick parameter horizon is read lane by lane), and how the library picks the mapping.
+Checker: the oracle (oracle/liboracle.so), same seeded inputs.
+Tolerances are SURVEY.md §8(c)'s (fp64 teacher-forced: |du| <= 1e-9, |dUdt| <= 1e-7 rel, Arnoldi counts equal); the
+loop under inputs: those of class_harness.compare_loop_inputs (u, x and the follow-up u within 1e-7, counts equal)."""
+from collections import namedtuple
+
 import numpy as np
 import pytest
 
 import cgmres_cpp_amd as cg
+import class_harness as harness
 from gpu_helpers import U_TOL, _refs, _teacher_forced
 
 pytestmark = pytest.mark.gpu
@@ -80,6 +86,44 @@ def test_horizon_lengths_at_the_row_boundaries_of_the_scans(orc, dv, km, model):
         r.set_state(0.7, U_o, d_o)
     _teacher_forced(orc, c, refs, x0, 3)
     c.close()
+
+
+WaveCase = namedtuple("WaveCase", "model dv k_max")
+WAVE_B = 5
+
+
+def _wave_batch(case, tol, variant=WAVE):
+    c = cg.CgmresBatch(case.model, batch=WAVE_B, dv=case.dv, k_max=case.k_max, tol=tol, variant=variant)
+    assert c.variant == variant and (variant != WAVE or c.variant_name == "wave"), c.variant_name
+    return c, WAVE_B
+
+
+def _wave_inputs_reference(orc, case, tol, leg):
+    x0, u0, p = orc.batch_scenario(case.model, harness.B16)
+    dims = orc.Controller(case.model, case.dv, case.k_max)
+    seq, d, v = harness.leg_of(leg, *harness.loop_inputs((dims.dim_x, dims.dim_p), case.dv, p, np.float64))
+    return harness.oracle_loop_inputs(orc, case.model, "f64", case.dv, case.k_max, tol, x0[:WAVE_B], u0[:WAVE_B], p[:WAVE_B], seq, d, v)
+
+
+WAVE_SIDE = harness.Side(None, "wave", "orc", None, _wave_batch, lambda orc, case, B: tuple(a[:B] for a in orc.batch_scenario(case.model, harness.B16)),
+                         lambda case, tol: harness.F64, "", _wave_inputs_reference)
+
+
+@pytest.mark.parametrize("model", [0, 2, 1])
+@pytest.mark.parametrize("dv,km", [(2, 2), (3, 5), (15, 4), (16, 10), (17, 3), (31, 6), (32, 6), (33, 10),
+                                    (47, 7), (48, 9), (49, 10), (62, 5), (63, 10)])
+def test_device_loop_with_disturbance_noise_and_moving_reference_at_the_row_boundaries(orc, dv, km, model):
+    """The horizons of test_horizon_lengths_at_the_row_boundaries_of_the_scans in the fused loop with all three per-tick
+    inputs (class_harness: the "all" leg, 12 ticks across a launch boundary and one plain tick behind them): the moving
+    reference is a per-tick horizon that this mapping reads one stage per lane, d and v enter at the plant step and at
+    y_0 = x_0 + v_0 of every launch.  The two oracle builds (with and without fused multiply-adds) stay within 1.5e-11
+    of each other at all 39 shapes, with equal counts."""
+    if model == 1 and 6 * dv > 320:
+        pytest.skip("dim_u*dv beyond the wg mapping, which serves the white-box hooks of a wave handle")
+    assert harness.LOOP_TICKS > cg.TICKS_PER_LAUNCH and cg.EXIT_NATURAL == harness.EXIT_NATURAL
+    bad, wu, wn = harness.loop_inputs_problems(WAVE_SIDE, orc, WaveCase(model, dv, km), 1e-6, "all")
+    print(f"wave model {model} dv {dv} k_max {km} inputs all: |du|,|dx|/bound {wu:.3g} follow-up |du|/bound {wn:.3g}")
+    assert not bad, (model, dv, km, len(bad), bad[:4])
 
 
 def test_exit_paths_of_gmres_on_the_pendulum(orc):

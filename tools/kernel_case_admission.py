@@ -5,6 +5,7 @@ the CPU, without a GPU and without the reference tree.
     python tools/kernel_case_admission.py --select   # choose members A and B of every class; print the CASES block
     python tools/kernel_case_admission.py --select --write   # ... and put it into tests/kernel_classes.py
     python tools/kernel_case_admission.py MODEL DTYPE DV KMAX   # figures of one candidate
+    python tools/kernel_case_admission.py --inputs   # every case under the per-tick inputs of the fused loop (below)
 
 Method (that of FP32_SPREAD in tests/test_gpu_tuning.py): the oracle is built a second time into a temporary directory
 through oracle/Makefile's CXXFLAGS override: the Makefile's own flags with -ffp-contract=fast -mfma in place of
@@ -30,7 +31,15 @@ A candidate that is not admitted with tol = 1e-6 is passed over for the next mem
 one that is admitted with tol = 1e-6 only gets fixed_k_ok = False.  kernel_classes.DEVICE_MISSES lists the shapes that were
 admitted here and that a kernel then missed on the device with the lane mapping inside its bounds: findings about that
 kernel, passed over in the same way and named in the table.  The selection, the check loop and the fp64 rule are those
-of tests/class_ledger.py, which tools/user_case_admission.py uses as well."""
+of tests/class_ledger.py, which tools/user_case_admission.py uses as well.
+
+--inputs: the GPU test also runs every case's 12-tick device loop under a moving reference ("ptau" leg) and under a
+moving reference, a process disturbance and a measurement noise ("all" leg), and one plain tick behind it
+(tests/class_harness.py: loop_inputs, oracle_loop_inputs).  The two builds run exactly that, each leg, each tolerance
+mode the test runs for the case, and a leg is admitted for a case under the loop margins above: fp64 within 1e-8 on u, x
+and the follow-up u with equal counts and reasons at the last tick and, with tol = 0, k_max iterations on every tick;
+fp32 within 1e-4 / 8.  What it leaves out must be exactly what kernel_classes.leg_skip leaves out, and no class may end
+without an admitted leg; its figures are the comment block above kernel_classes.leg_applies."""
 import math
 import os
 import shutil
@@ -43,6 +52,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+import class_harness as harness  # noqa: E402
 import class_ledger as ledger  # noqa: E402
 import kernel_classes as kc  # noqa: E402
 import plan_probe  # noqa: E402
@@ -191,9 +201,79 @@ def select():
     return ledger.select(kc, kc.members(plan_probe.probe()), admission, figures, row, label)
 
 
+def measure_inputs(case, tol, leg):
+    """The two builds free-running under the leg's sequences of class_harness.loop_inputs, follow-up tick included:
+    (worst |du|, |dx| and follow-up |du| between them after the last tick, last tick's counts and reasons equal, every
+    count of every tick of the plain build = k_max)."""
+    x0, u0, p = orc.batch_scenario(case.model, N_INST)
+    dims = orc.Controller(case.model, case.dv, case.k_max)
+    npdt = np.float32 if case.dtype == 1 else np.float64
+    seq, d, v = harness.leg_of(leg, *harness.loop_inputs((dims.dim_x, dims.dim_p), case.dv, p, npdt))
+    a, b = (harness.oracle_loop_inputs(orc, case.model, kc.DTYPE_NAMES[case.dtype], case.dv, case.k_max, tol, x0, u0, p,
+                                       seq, d, v, which=which) for which in ("oracle", "fast"))
+    s = 0.0
+    for q in ("u", "x", "u_next"):
+        s = worse(s, float(np.max(np.abs(a[q] - b[q]))))
+    agree = bool(np.array_equal(a["k"], b["k"]) and np.array_equal(a["reason"], b["reason"]))
+    return s, agree, bool(np.all(a["full"]))
+
+
+def inputs_admitted(case, tol, s, agree, full):
+    """the loop margins of the rule above: fp64 a tenth of the device bound with equal counts and reasons at the last tick
+    and, with tol = 0, k_max iterations on every tick; fp32 an eighth of the device bound"""
+    if case.dtype == 1:
+        return s <= F32_LOOP
+    return s <= ledger.F64_LOOP and agree and (tol > 0 or full)
+
+
+def inputs():
+    """Every case of CASES under the per-tick inputs of the GPU test's two legs, each tolerance mode the test runs: one
+    line per case, the worst figure per leg and dtype, and whether kernel_classes.leg_skip is exactly what the
+    measurement leaves out.  0 when it is and every class keeps an admitted case."""
+    shapes, worst, out, held, pairs = {}, {}, {}, set(), set()
+    for case in kc.RECORDS:
+        words = []
+        for leg in harness.LEGS:
+            if not kc.leg_applies(case, leg):
+                continue
+            ok = True
+            for tol in TOLS if case.fixed_k_ok else TOLS[:1]:
+                key = (case.model, case.dtype, case.dv, case.k_max, tol, leg)
+                pairs.add(key[:5])
+                if key not in shapes:
+                    shapes[key] = measure_inputs(case, tol, leg)
+                s, agree, full = shapes[key]
+                adm = inputs_admitted(case, tol, s, agree, full)
+                ok = ok and adm
+                words.append("%s tol %g: %.1e %s%s%s" % (leg, tol, s, "agree" if agree else "COUNTS DIFFER",
+                                                        "" if full else ", early exits", "" if adm else " NOT ADMITTED"))
+                group = (leg, kc.DTYPE_NAMES[case.dtype], kc.MODEL_NAMES[case.model], adm)
+                lo, hi = worst.get(group, (math.inf, 0.0))
+                worst[group] = (min(lo, s), worse(hi, s))
+            out[(kc.key(case), leg)] = ok
+            if ok:
+                held.add(case.cls)
+        print("%-40s %s" % (kc.case_id(case), " | ".join(words)))
+    for (leg, dt, model, adm), (lo, hi) in sorted(worst.items()):
+        print("leg %-4s %s %-10s %s: %.1e .. %.1e" % (leg, dt, model, "admitted" if adm else "NOT ADMITTED", lo, hi))
+    rejected = sorted(k for k, ok in out.items() if not ok)
+    skipped = sorted((kc.key(c), leg) for c in kc.RECORDS for leg in harness.LEGS if kc.leg_applies(c, leg) and kc.leg_skip(c, leg))
+    bare = sorted({c.cls for c in kc.RECORDS} - held)
+    print("%d cases, %d shape/tolerance pairs; ptau leg: %d cases, all leg: %d cases; %d not admitted, %d skipped by the rule"
+          % (len(kc.RECORDS), len(pairs), sum(leg == "ptau" for _, leg in out), sum(leg == "all" for _, leg in out),
+             len(rejected), len(skipped)))
+    if rejected != skipped:
+        print("THE RULE OF kernel_classes.leg_skip DIFFERS FROM THE MEASUREMENT:", sorted(set(rejected) ^ set(skipped)))
+    if bare:
+        print("CLASSES WITHOUT AN ADMITTED LEG:", [kc.class_name(c) for c in bare])
+    return 1 if rejected != skipped or bare else 0
+
+
 def main(argv):
     tmp = build_fast_flavour()
     try:
+        if "--inputs" in argv:
+            return inputs()
         if "--select" in argv:
             text = select()
             print(text)
