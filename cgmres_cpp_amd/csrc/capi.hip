@@ -63,19 +63,84 @@ const OpPlugin* find_op(int id) {
   return id >= 0 && id < int(op_plugins().size()) ? &op_plugins()[id] : nullptr;
 }
 
+// Opens a plugin of either kind and files its record in `reg`; *index receives its place there (that of the earlier
+// record when the path is registered already).  `kind` is "model" or "operator", `prefix` what its symbols start with;
+// `syms` names the symbols behind the ABI one and where their addresses go in `pl`, `check` fills the rest of `pl` and
+// refuses bad dimensions.
+struct Sym {
+  const char* name;
+  void* slot;  // address of a function-pointer member of the record
+  bool required;
+};
+template <class Rec, class Check>
+int open_plugin(std::deque<Rec>& reg, const char* kind, const std::string& prefix, const char* path, int32_t* index, Rec& pl,
+                std::initializer_list<Sym> syms, Check check) {
+  if (!path || !index) return fail(CGMRES_HIP_EINVAL, "register_%s: null argument", kind);
+  {
+    std::lock_guard<std::mutex> g(plugins_mutex());
+    for (size_t n = 0; n < reg.size(); ++n)
+      if (reg[n].path == path) {
+        *index = int(n);
+        return 0;
+      }
+  }
+  void* dl = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+  if (!dl) return fail(CGMRES_HIP_EINVAL, "register_%s: %s", kind, dlerror());
+  pl.dl = dl, pl.path = path;
+  auto abi = reinterpret_cast<int32_t (*)(void)>(dlsym(dl, (prefix + "abi").c_str()));
+  bool all = abi != nullptr;
+  for (const Sym& s : syms) {
+    void* f = dlsym(dl, (prefix + s.name).c_str());
+    std::memcpy(s.slot, &f, sizeof f);
+    all = all && (f || !s.required);
+  }
+  int rc = 0;
+  if (!all)
+    rc = fail(CGMRES_HIP_EINVAL, "register_%s: %s is not a cgmres_hip %s plugin", kind, path, kind);
+  else if (abi() != CGMRES_HIP_ABI_VERSION)
+    rc = fail(CGMRES_HIP_EINVAL, "register_%s: plugin ABI %d, library has %d", kind, abi(), CGMRES_HIP_ABI_VERSION);
+  else
+    rc = check(pl);
+  if (rc) {
+    dlclose(dl);
+    return rc;
+  }
+  std::lock_guard<std::mutex> g(plugins_mutex());
+  reg.push_back(pl);
+  *index = int(reg.size()) - 1;
+  return 0;
+}
+
+// The built-in models, dispatched in one place: f is called with a tag that names the device model and the two
+// factories of its translation units (inst_*.hip); false for an id that is none of them.
+template <template <class> class M>
+struct Builtin {
+  using Dev = M<double>;
+  cgmres_hip_ctx* (*make_f64)(const cgmres_hip_config&, int*);
+  cgmres_hip_ctx* (*make_f32)(const cgmres_hip_config&, int*);
+};
+template <class F>
+bool with_builtin(int id, F&& f) {
+  switch (id) {
+    case CGMRES_HIP_MODEL_PENDULUM:
+      f(Builtin<cgm::PendulumDev>{cgm::make_pendulum_f64, cgm::make_pendulum_f32});
+      return true;
+    case CGMRES_HIP_MODEL_MSD:
+      f(Builtin<cgm::MsdDev>{cgm::make_msd_f64, cgm::make_msd_f32});
+      return true;
+    case CGMRES_HIP_MODEL_SEMIACTIVE:
+      f(Builtin<cgm::SemiactiveDev>{cgm::make_semiactive_f64, cgm::make_semiactive_f32});
+      return true;
+  }
+  return false;
+}
+
 cgm::ModelInfo model_info(int id, bool* ok) {
   *ok = true;
   if (const Plugin* pl = find_plugin(id)) return pl->info;
-  switch (id) {
-    case CGMRES_HIP_MODEL_PENDULUM:
-      return cgm::PendulumDev<double>::info();
-    case CGMRES_HIP_MODEL_MSD:
-      return cgm::MsdDev<double>::info();
-    case CGMRES_HIP_MODEL_SEMIACTIVE:
-      return cgm::SemiactiveDev<double>::info();
-  }
-  *ok = false;
-  return {};
+  cgm::ModelInfo mi{};
+  *ok = with_builtin(id, [&](auto m) { mi = decltype(m)::Dev::info(); });
+  return mi;
 }
 
 int check_device(int device) {
@@ -96,15 +161,20 @@ cgmres_hip_ctx* make_ctx(const cgmres_hip_config& cfg, int* resolved) {
     *resolved = cfg.variant;
     return pl->make(&cfg);
   }
-  switch (cfg.model_id) {
-    case CGMRES_HIP_MODEL_PENDULUM:
-      return f32 ? cgm::make_pendulum_f32(cfg, resolved) : cgm::make_pendulum_f64(cfg, resolved);
-    case CGMRES_HIP_MODEL_MSD:
-      return f32 ? cgm::make_msd_f32(cfg, resolved) : cgm::make_msd_f64(cfg, resolved);
-    case CGMRES_HIP_MODEL_SEMIACTIVE:
-      return f32 ? cgm::make_semiactive_f32(cfg, resolved) : cgm::make_semiactive_f64(cfg, resolved);
-  }
-  return nullptr;
+  cgmres_hip_ctx* c = nullptr;
+  with_builtin(cfg.model_id, [&](auto m) { c = (f32 ? m.make_f32 : m.make_f64)(cfg, resolved); });
+  return c;
+}
+
+int enter(cgmres_hip_handle h, bool ok = true, const char* what = nullptr) {
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  return ok ? 0 : fail(CGMRES_HIP_EINVAL, "%s", what);
+}
+
+// what the three closed-loop entry points end in
+int closed_loop(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const cgm::LoopSeqs& sq) {
+  if (int rc = enter(h, u && x, "closed_loop: null pointer")) return rc;
+  return h->closed_loop(x, u, n_ticks, sq);
 }
 
 __global__ void sincos_selftest_kernel(const double* a, double* s, double* c, int n) {
@@ -116,6 +186,11 @@ __global__ void sincos_selftest_kernel(const double* a, double* s, double* c, in
 
 #define NEED(h) \
   if (!(h)) return fail(CGMRES_HIP_EINVAL, "%s: null handle", __func__)
+// Where a call on a handle, past NEED and whatever the entry point refuses before it touches a device, enters the
+// library: the handle's device (the contexts select none themselves), then, where given, the condition on the arguments
+// that is refused with the text `what`.
+#define ENTER(h, ...) \
+  if (int rc_ = enter(h, ##__VA_ARGS__)) return rc_
 
 extern "C" {
 
@@ -172,16 +247,7 @@ int cgmres_hip_model_probe(int32_t model_id, int32_t device, const double* x, co
     if (const Plugin* pl = find_plugin(model_id)) {
       if (pl->probe(dx, du, dp, dl, dout, nullptr) != 0) e = hipErrorLaunchFailure;
     } else {
-      switch (model_id) {
-        case CGMRES_HIP_MODEL_PENDULUM:
-          cgm::probe_kernel<cgm::PendulumDev<double>><<<1, 1>>>(dx, du, dp, dl, dout);
-          break;
-        case CGMRES_HIP_MODEL_MSD:
-          cgm::probe_kernel<cgm::MsdDev<double>><<<1, 1>>>(dx, du, dp, dl, dout);
-          break;
-        default:
-          cgm::probe_kernel<cgm::SemiactiveDev<double>><<<1, 1>>>(dx, du, dp, dl, dout);
-      }
+      with_builtin(model_id, [&](auto m) { cgm::probe_kernel<typename decltype(m)::Dev><<<1, 1>>>(dx, du, dp, dl, dout); });
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();  // (execution errors of the probe kernel surface here)
@@ -215,84 +281,39 @@ int cgmres_hip_selftest_sincos(int32_t device, const double* a, int32_t n, doubl
 }
 
 int cgmres_hip_register_model(const char* plugin_path, int32_t* model_id) {
-  if (!plugin_path || !model_id) return fail(CGMRES_HIP_EINVAL, "register_model: null argument");
-  {
-    std::lock_guard<std::mutex> g(plugins_mutex());
-    for (size_t n = 0; n < plugins().size(); ++n)
-      if (plugins()[n].path == plugin_path) {
-        *model_id = CGMRES_HIP_MODEL_USER_BASE + int(n);
-        return 0;
-      }
-  }
-  void* dl = dlopen(plugin_path, RTLD_NOW | RTLD_LOCAL);
-  if (!dl) return fail(CGMRES_HIP_EINVAL, "register_model: %s", dlerror());
-  auto abi = reinterpret_cast<int32_t (*)(void)>(dlsym(dl, "cgmres_hip_plugin_abi"));
-  auto info = reinterpret_cast<void (*)(int32_t*, double*)>(dlsym(dl, "cgmres_hip_plugin_info"));
   Plugin pl{};
-  pl.dl = dl, pl.path = plugin_path;
-  pl.make = reinterpret_cast<decltype(pl.make)>(dlsym(dl, "cgmres_hip_plugin_make"));
-  pl.probe = reinterpret_cast<decltype(pl.probe)>(dlsym(dl, "cgmres_hip_plugin_probe"));
-  pl.last_error = reinterpret_cast<decltype(pl.last_error)>(dlsym(dl, "cgmres_hip_plugin_last_error"));
-  if (!abi || !info || !pl.make || !pl.probe || !pl.last_error) {
-    dlclose(dl);
-    return fail(CGMRES_HIP_EINVAL, "register_model: %s is not a cgmres_hip model plugin", plugin_path);
-  }
-  if (abi() != CGMRES_HIP_ABI_VERSION) {
-    dlclose(dl);
-    return fail(CGMRES_HIP_EINVAL, "register_model: plugin ABI %d, library has %d", abi(), CGMRES_HIP_ABI_VERSION);
-  }
-  int32_t dims[5];
-  double tun[6];
-  info(dims, tun);
-  pl.info = {dims[0], dims[1], dims[2], dims[3], dims[4], tun[0], tun[1], tun[2], tun[3], tun[4], tun[5]};
-  if (dims[0] < 1 || dims[1] < 1 || dims[2] < 0) {
-    dlclose(dl);
-    return fail(CGMRES_HIP_EINVAL, "register_model: bad dimensions %d/%d/%d", dims[0], dims[1], dims[2]);
-  }
-  std::lock_guard<std::mutex> g(plugins_mutex());
-  plugins().push_back(pl);
-  *model_id = CGMRES_HIP_MODEL_USER_BASE + int(plugins().size()) - 1;
-  return 0;
+  void (*info)(int32_t*, double*) = nullptr;
+  int32_t n = 0;
+  const int rc = open_plugin(
+      plugins(), "model", "cgmres_hip_plugin_", plugin_path, model_id ? &n : nullptr, pl,
+      {{"info", &info, true}, {"make", &pl.make, true}, {"probe", &pl.probe, true}, {"last_error", &pl.last_error, true}},
+      [&](Plugin& q) {
+        int32_t dims[5];
+        double tun[6];
+        info(dims, tun);
+        q.info = {dims[0], dims[1], dims[2], dims[3], dims[4], tun[0], tun[1], tun[2], tun[3], tun[4], tun[5]};
+        if (dims[0] < 1 || dims[1] < 1 || dims[2] < 0)
+          return fail(CGMRES_HIP_EINVAL, "register_model: bad dimensions %d/%d/%d", dims[0], dims[1], dims[2]);
+        return 0;
+      });
+  if (!rc) *model_id = CGMRES_HIP_MODEL_USER_BASE + n;
+  return rc;
 }
 
 int cgmres_hip_register_operator(const char* plugin_path, int32_t* op_id) {
-  if (!plugin_path || !op_id) return fail(CGMRES_HIP_EINVAL, "register_operator: null argument");
-  {
-    std::lock_guard<std::mutex> g(plugins_mutex());
-    for (size_t n = 0; n < op_plugins().size(); ++n)
-      if (op_plugins()[n].path == plugin_path) {
-        *op_id = int(n);
-        return 0;
-      }
-  }
-  void* dl = dlopen(plugin_path, RTLD_NOW | RTLD_LOCAL);
-  if (!dl) return fail(CGMRES_HIP_EINVAL, "register_operator: %s", dlerror());
-  auto abi = reinterpret_cast<int32_t (*)(void)>(dlsym(dl, "cgmres_hip_opplugin_abi"));
-  auto info = reinterpret_cast<void (*)(int32_t*)>(dlsym(dl, "cgmres_hip_opplugin_info"));
   OpPlugin pl{};
-  pl.dl = dl, pl.path = plugin_path;
-  pl.solve = reinterpret_cast<decltype(pl.solve)>(dlsym(dl, "cgmres_hip_opplugin_solve"));
-  pl.last_error = reinterpret_cast<decltype(pl.last_error)>(dlsym(dl, "cgmres_hip_opplugin_last_error"));
-  pl.plan = reinterpret_cast<decltype(pl.plan)>(dlsym(dl, "cgmres_hip_opplugin_plan"));
-  if (!abi || !info || !pl.solve || !pl.last_error) {
-    dlclose(dl);
-    return fail(CGMRES_HIP_EINVAL, "register_operator: %s is not a cgmres_hip operator plugin", plugin_path);
-  }
-  if (abi() != CGMRES_HIP_ABI_VERSION) {
-    dlclose(dl);
-    return fail(CGMRES_HIP_EINVAL, "register_operator: plugin ABI %d, library has %d", abi(), CGMRES_HIP_ABI_VERSION);
-  }
-  int32_t dims[2];
-  info(dims);
-  pl.len = dims[0], pl.n_params = dims[1];
-  if (pl.len < 1 || pl.n_params < 0) {
-    dlclose(dl);
-    return fail(CGMRES_HIP_EINVAL, "register_operator: bad dimensions %d/%d", dims[0], dims[1]);
-  }
-  std::lock_guard<std::mutex> g(plugins_mutex());
-  op_plugins().push_back(pl);
-  *op_id = int(op_plugins().size()) - 1;
-  return 0;
+  void (*info)(int32_t*) = nullptr;
+  // (plan: an optional symbol, see OpPlugin)
+  return open_plugin(op_plugins(), "operator", "cgmres_hip_opplugin_", plugin_path, op_id, pl,
+                     {{"info", &info, true}, {"solve", &pl.solve, true}, {"last_error", &pl.last_error, true}, {"plan", &pl.plan, false}},
+                     [&](OpPlugin& q) {
+                       int32_t dims[2];
+                       info(dims);
+                       q.len = dims[0], q.n_params = dims[1];
+                       if (q.len < 1 || q.n_params < 0)
+                         return fail(CGMRES_HIP_EINVAL, "register_operator: bad dimensions %d/%d", dims[0], dims[1]);
+                       return 0;
+                     });
 }
 
 int cgmres_hip_operator_info(int32_t op_id, int32_t dims[2]) {
@@ -382,18 +403,23 @@ int cgmres_hip_get_config(cgmres_hip_handle h, cgmres_hip_config* cfg) {
 const char* cgmres_hip_variant_name(cgmres_hip_handle h) { return h ? h->variant_name() : nullptr; }
 int cgmres_hip_set_ptau(cgmres_hip_handle h, const void* p, int per_instance) {
   NEED(h);
+  ENTER(h, h->np == 0 || p, "set_ptau: null pointer");
   return h->set_ptau(p, per_instance, false);
 }
 int cgmres_hip_set_ptau_repeat(cgmres_hip_handle h, const void* p, int per_instance) {
   NEED(h);
+  ENTER(h, h->np == 0 || p, "set_ptau: null pointer");
   return h->set_ptau(p, per_instance, true);
 }
 int cgmres_hip_init_u0(cgmres_hip_handle h, const void* u0, int per_instance) {
   NEED(h);
+  ENTER(h, u0, "init_u0: null pointer");
   return h->init_u0(u0, per_instance);
 }
 int cgmres_hip_init_u0_newton(cgmres_hip_handle h, void* u0, const void* x0, const void* p0, int32_t n_loop) {
   NEED(h);
+  ENTER(h, u0 && x0 && (h->np == 0 || p0), "init_u0_newton: null pointer");
+  if (n_loop < 0) return fail(CGMRES_HIP_EINVAL, "init_u0_newton: n_loop < 0");
   return h->init_u0_newton(u0, x0, p0, n_loop);
 }
 // The reference's DEBUG_MODE builds exit(-1) when an output argument aliases an input (cgmres.hpp:119-124,
@@ -401,17 +427,19 @@ int cgmres_hip_init_u0_newton(cgmres_hip_handle h, void* u0, const void* x0, con
 int cgmres_hip_control(cgmres_hip_handle h, void* u, const void* x) {
   NEED(h);
   if (u && u == x) return fail(CGMRES_HIP_EINVAL, "control: u and x are the same buffer (cgmres.hpp DEBUG_MODE alias guard)");
+  ENTER(h, u && x, "control: null pointer");
   return h->control_host(u, x);
 }
 int cgmres_hip_control_device(cgmres_hip_handle h, void* u, const void* x) {
   NEED(h);
   if (u && u == x) return fail(CGMRES_HIP_EINVAL, "control_device: u and x are the same buffer (cgmres.hpp DEBUG_MODE alias guard)");
+  ENTER(h, u && x, "control: null pointer");
   return h->control_device(u, x, nullptr);
 }
 int cgmres_hip_closed_loop_device(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks) {
   NEED(h);
   if (n_ticks < 0) return fail(CGMRES_HIP_EINVAL, "n_ticks < 0");
-  return h->closed_loop(x, u, n_ticks, cgm::LoopSeqs{});
+  return closed_loop(h, x, u, n_ticks, cgm::LoopSeqs{});
 }
 int cgmres_hip_closed_loop_device_ptau(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const void* ptau_seq,
                                        int per_instance) {
@@ -420,7 +448,7 @@ int cgmres_hip_closed_loop_device_ptau(cgmres_hip_handle h, void* x, void* u, in
   if (h->np && !ptau_seq) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ptau: null ptau sequence");
   cgm::LoopSeqs sq;
   sq.ptau = h->np ? ptau_seq : nullptr, sq.ptau_per_instance = per_instance;
-  return h->closed_loop(x, u, n_ticks, sq);
+  return closed_loop(h, x, u, n_ticks, sq);
 }
 int cgmres_hip_closed_loop_device_ex(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const cgmres_hip_loop_inputs* in) {
   NEED(h);
@@ -453,7 +481,7 @@ int cgmres_hip_closed_loop_device_ex(cgmres_hip_handle h, void* x, void* u, int3
     sq.dist = in->dist_seq_dev, sq.dist_per_instance = in->dist_per_instance;
     sq.meas = in->meas_seq_dev, sq.meas_per_instance = in->meas_per_instance;
   }
-  return h->closed_loop(x, u, n_ticks, sq);
+  return closed_loop(h, x, u, n_ticks, sq);
 }
 int cgmres_hip_shard_bounds(int32_t n, int32_t world, int32_t rank, int32_t* lo, int32_t* hi) {
   if (n < 0 || world < 1 || rank < 0 || rank >= world || !lo || !hi)
@@ -465,7 +493,7 @@ int cgmres_hip_shard_bounds(int32_t n, int32_t world, int32_t rank, int32_t* lo,
 }
 int cgmres_hip_synchronize(cgmres_hip_handle h) {
   NEED(h);
-  HIP_TRY(hipSetDevice(h->cfg.device));
+  ENTER(h);
   HIP_TRY(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -476,10 +504,12 @@ int cgmres_hip_get_time(cgmres_hip_handle h, double* t) {
 }
 int cgmres_hip_get_state(cgmres_hip_handle h, double* t, void* U, void* dUdt) {
   NEED(h);
+  ENTER(h);
   return h->get_state(t, U, dUdt);
 }
 int cgmres_hip_set_state(cgmres_hip_handle h, double t, const void* U, const void* dUdt) {
   NEED(h);
+  ENTER(h);
   return h->set_state(t, U, dUdt);
 }
 int cgmres_hip_state_rows(cgmres_hip_handle h, void** U, void** dUdt, int32_t* pitch) {
@@ -489,44 +519,50 @@ int cgmres_hip_state_rows(cgmres_hip_handle h, void** U, void** dUdt, int32_t* p
 }
 int cgmres_hip_get_status(cgmres_hip_handle h, int32_t* n_ax, int32_t* reason) {
   NEED(h);
+  ENTER(h);
   return h->get_status(n_ax, reason);
 }
 int cgmres_hip_get_krylov(cgmres_hip_handle h, void* V, void* H, void* rho, void* g) {
   NEED(h);
+  ENTER(h);
   return h->get_krylov(V, H, rho, g);
 }
 int cgmres_hip_F_func(cgmres_hip_handle h, void* ret, const void* U, const void* x, double t) {
   NEED(h);
   if (!ret || !U || !x) return fail(CGMRES_HIP_EINVAL, "F_func: null pointer");
   if (ret == U || ret == x) return fail(CGMRES_HIP_EINVAL, "F_func: ret aliases an input (cgmres.hpp:119-124)");
+  ENTER(h);
   return h->hook_F(ret, U, x, t);
 }
 int cgmres_hip_prepare(cgmres_hip_handle h, void* b, const void* x) {
   NEED(h);
   if (!x) return fail(CGMRES_HIP_EINVAL, "prepare: null pointer");
+  ENTER(h);
   return h->hook_prepare(b, x);
 }
 int cgmres_hip_Ax_func(cgmres_hip_handle h, void* out, const void* v) {
   NEED(h);
   if (!out || !v) return fail(CGMRES_HIP_EINVAL, "Ax_func: null pointer");
   if (out == v) return fail(CGMRES_HIP_EINVAL, "Ax_func: Ax aliases v (cgmres.hpp:119-124)");
+  ENTER(h);
   return h->hook_Ax(out, v);
 }
 int cgmres_hip_gmres(cgmres_hip_handle h, void* x, const void* b) {
   NEED(h);
   if (!x || !b) return fail(CGMRES_HIP_EINVAL, "gmres: null pointer");
   if (x == b) return fail(CGMRES_HIP_EINVAL, "gmres: x aliases b (matrix.hpp:76-81)");
+  ENTER(h);
   return h->hook_gmres(x, b);
 }
 int cgmres_hip_timer_start(cgmres_hip_handle h) {
   NEED(h);
-  HIP_TRY(hipSetDevice(h->cfg.device));
+  ENTER(h);
   HIP_TRY(hipEventRecord(h->ev0, h->stream));
   return 0;
 }
 int cgmres_hip_timer_stop(cgmres_hip_handle h, float* ms) {
   NEED(h);
-  HIP_TRY(hipSetDevice(h->cfg.device));
+  ENTER(h);
   HIP_TRY(hipEventRecord(h->ev1, h->stream));
   HIP_TRY(hipEventSynchronize(h->ev1));
   float v = 0;
@@ -537,27 +573,27 @@ int cgmres_hip_timer_stop(cgmres_hip_handle h, float* ms) {
 int cgmres_hip_malloc(cgmres_hip_handle h, void** p, uint64_t bytes) {
   NEED(h);
   if (!p) return fail(CGMRES_HIP_EINVAL, "malloc: null pointer");
-  HIP_TRY(hipSetDevice(h->cfg.device));
+  ENTER(h);
   HIP_TRY(hipMalloc(p, bytes ? bytes : 1));
   return 0;
 }
 int cgmres_hip_free(cgmres_hip_handle h, void* p) {
   NEED(h);
-  HIP_TRY(hipSetDevice(h->cfg.device));
+  ENTER(h);
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipFree(p));
   return 0;
 }
 int cgmres_hip_memcpy_h2d(cgmres_hip_handle h, void* dst, const void* src, uint64_t bytes) {
   NEED(h);
-  HIP_TRY(hipSetDevice(h->cfg.device));
+  ENTER(h);
   HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return 0;
 }
 int cgmres_hip_memcpy_d2h(cgmres_hip_handle h, void* dst, const void* src, uint64_t bytes) {
   NEED(h);
-  HIP_TRY(hipSetDevice(h->cfg.device));
+  ENTER(h);
   HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return 0;

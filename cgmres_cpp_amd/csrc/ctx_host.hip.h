@@ -1,0 +1,77 @@
+// What the host side of the two kernel mappings has in common (ctx_lane.hip.h, ctx_wg.hip.h): the time of the batch,
+// the staged host-pointer tick, the solver status, the start-up Newton solve and the argument handling of set_ptau /
+// init_u0.  The device and the pointers of a call are checked where it enters the library (capi.hip: ENTER); a
+// context selects the device in init_common() and in its destructor only.
+//
+// D is the mapping's context (CRTP, no new virtual).  It provides
+//   P                                       its kernel parameters; both name the status arrays n_ax and reason
+//   launch_tick(u_out, x_in, x_next)        one control tick on the stream, advancing t
+//   upload(dst, pitch, src, n, reps, per_instance)
+//                                           host [B or 1][n] -> the mapping's device layout, every instance's n values
+//                                           repeated reps times (0: copied once, no repetition kernel)
+//   spread_u0(du)                           device [B][nu] -> P.U, repeated over the horizon
+//   pitch_U()                               what upload() takes as the pitch of P.U
+#pragma once
+#include "ctx_common.hip.h"
+#include "util_kernels.hip.h"
+
+namespace cgm {
+
+template <class M, class T, class D>
+struct CtxHost : cgmres_hip_ctx {
+  T t = T(0);
+  T *stage = nullptr, *stage2 = nullptr;  // device staging, grown on demand: upload(), and init_u0_newton / the hooks
+  size_t stage_n = 0, stage2_n = 0;
+  T *x_dev = nullptr, *u_dev = nullptr;  // [B][nx], [B][nu] staging for the host-pointer entry points
+
+  D& self() { return static_cast<D&>(*this); }
+
+  T dtau_of(T tt) const {  // cgmres.hpp:32-34, evaluated once per tick on the host for the whole batch
+    return T(cfg.Tf) * (1 - std::exp(-T(cfg.alpha) * tt)) / T(cfg.dv);
+  }
+  double time() const override { return double(t); }
+
+  int set_ptau(const void* p, int per_instance, bool repeat) override {
+    if (np == 0) return 0;  // semiactive: ptau is a zero-length array (semiactive_damper/main.cpp:45-47)
+    const int all = np * (cfg.dv + 1);
+    return repeat ? self().upload(self().P.ptau, all, p, np, cfg.dv + 1, per_instance)
+                  : self().upload(self().P.ptau, all, p, all, 0, per_instance);
+  }
+  int init_u0(const void* u0, int per_instance) override {
+    return self().upload(self().P.U, self().pitch_U(), u0, nu, cfg.dv, per_instance);
+  }
+  int init_u0_newton(void* u0, const void* x0, const void* p0, int n_loop) override {
+    const size_t B = cfg.batch;
+    if (int rc = grow(&stage2, &stage2_n, B * (nu + nx + np))) return rc;
+    T *du = stage2, *dx = du + B * nu, *dp = dx + B * nx;
+    HIP_TRY(hipMemcpyAsync(du, u0, B * nu * sizeof(T), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(dx, x0, B * nx * sizeof(T), hipMemcpyHostToDevice, stream));
+    if (np) HIP_TRY(hipMemcpyAsync(dp, p0, B * np * sizeof(T), hipMemcpyHostToDevice, stream));
+    newton_u0_kernel<M, T><<<dim3((B + 63) / 64), 64, 0, stream>>>(du, dx, dp, cfg.batch, n_loop);
+    HIP_TRY(hipGetLastError());
+    if (int rc = self().spread_u0(du)) return rc;  // cgmres.hpp:75
+    HIP_TRY(hipMemcpyAsync(u0, du, B * nu * sizeof(T), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+  }
+
+  int control_device(void* u, const void* x, void* x_next) override {
+    return self().launch_tick(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x_next));
+  }
+  int control_host(void* u, const void* x) override {  // staged: copy in, launch, copy out, synchronise
+    HIP_TRY(hipMemcpyAsync(x_dev, x, size_t(cfg.batch) * nx * sizeof(T), hipMemcpyHostToDevice, stream));
+    if (int rc = self().launch_tick(u_dev, x_dev, nullptr)) return rc;
+    HIP_TRY(hipMemcpyAsync(u, u_dev, size_t(cfg.batch) * nu * sizeof(T), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+  }
+
+  int get_status(int32_t* n_ax, int32_t* reason) override {
+    if (n_ax) HIP_TRY(hipMemcpyAsync(n_ax, self().P.n_ax, size_t(cfg.batch) * 4, hipMemcpyDeviceToHost, stream));
+    if (reason) HIP_TRY(hipMemcpyAsync(reason, self().P.reason, size_t(cfg.batch) * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+  }
+};
+
+}  // namespace cgm

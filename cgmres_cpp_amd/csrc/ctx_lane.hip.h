@@ -2,18 +2,17 @@
 #pragma once
 #include "ctx_common.hip.h"
 #include "tick_lane.hip.h"
-#include "util_kernels.hip.h"
+#include "ctx_host.hip.h"
 
 namespace cgm {
 
 template <class M, class T>
-struct CtxLane final : cgmres_hip_ctx {
+struct CtxLane final : CtxHost<M, T, CtxLane<M, T>> {
+  using Host = CtxHost<M, T, CtxLane<M, T>>;
+  using Host::cfg, Host::nx, Host::nu, Host::np, Host::L, Host::stream, Host::dalloc, Host::grow, Host::init_common;
+  using Host::t, Host::dtau_of, Host::stage, Host::stage_n, Host::stage2, Host::stage2_n, Host::x_dev, Host::u_dev;
   TickParams<T> P{};
-  T t = T(0);
   int ldb = 0;
-  T *stage_a = nullptr, *stage_b = nullptr;  // device staging, grown on demand
-  size_t stage_a_n = 0, stage_b_n = 0;
-  T *x_dev = nullptr, *u_dev = nullptr;  // [B][nx], [B][nu] staging for the host-pointer entry points
 
   const char* variant_name() const override { return "lane"; }
 
@@ -42,20 +41,16 @@ struct CtxLane final : cgmres_hip_ctx {
   }
 
   dim3 lane_grid() const { return dim3((cfg.batch + 63) / 64); }
-  T dtau_of(T tt) const {  // cgmres.hpp:32-34, evaluated once per tick on the host for the whole batch
-    return T(cfg.Tf) * (1 - std::exp(-T(cfg.alpha) * tt)) / T(cfg.dv);
-  }
-
-  // host instance-major [B or 1][n] -> device element-major [n*rep][ldb]
-  int upload(T* dst, const void* src, int n, int per_instance, int stages_rep) {
+  // host instance-major [B or 1][n] -> device element-major [n*reps][ldb] (the pitch of every such array is ldb)
+  int upload(T* dst, size_t, const void* src, int n, int reps, int per_instance) {
     const size_t cnt = size_t(per_instance ? cfg.batch : 1) * n;
-    if (int rc = grow(&stage_a, &stage_a_n, cnt)) return rc;
-    HIP_TRY(hipMemcpyAsync(stage_a, src, cnt * sizeof(T), hipMemcpyHostToDevice, stream));
-    dim3 grid((cfg.batch + 255) / 256, n * (stages_rep ? stages_rep : 1));
-    if (stages_rep)
-      replicate_stages<T><<<grid, 256, 0, stream>>>(dst, stage_a, cfg.batch, ldb, n, stages_rep, !per_instance);
+    if (int rc = grow(&stage, &stage_n, cnt)) return rc;
+    HIP_TRY(hipMemcpyAsync(stage, src, cnt * sizeof(T), hipMemcpyHostToDevice, stream));
+    dim3 grid((cfg.batch + 255) / 256, n * (reps ? reps : 1));
+    if (reps)
+      replicate_stages<T><<<grid, 256, 0, stream>>>(dst, stage, cfg.batch, ldb, n, reps, !per_instance);
     else
-      to_element_major<T><<<grid, 256, 0, stream>>>(dst, stage_a, cfg.batch, ldb, n, !per_instance);
+      to_element_major<T><<<grid, 256, 0, stream>>>(dst, stage, cfg.batch, ldb, n, !per_instance);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));  // the host buffer may be reused by the caller right away
     return 0;
@@ -63,43 +58,20 @@ struct CtxLane final : cgmres_hip_ctx {
   int download(void* dst, const T* src, int n) {
     if (!dst) return 0;
     const size_t cnt = size_t(cfg.batch) * n;
-    if (int rc = grow(&stage_a, &stage_a_n, cnt)) return rc;
+    if (int rc = grow(&stage, &stage_n, cnt)) return rc;
     dim3 grid((cfg.batch + 255) / 256, n);
-    to_instance_major<T><<<grid, 256, 0, stream>>>(stage_a, src, cfg.batch, ldb, n);
+    to_instance_major<T><<<grid, 256, 0, stream>>>(stage, src, cfg.batch, ldb, n);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(dst, stage_a, cnt * sizeof(T), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(dst, stage, cnt * sizeof(T), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
   }
 
-  int set_ptau(const void* p, int per_instance, bool repeat) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (np == 0) return 0;  // semiactive: ptau is a zero-length array (semiactive_damper/main.cpp:45-47)
-    if (!p) return fail(CGMRES_HIP_EINVAL, "set_ptau: null pointer");
-    return repeat ? upload(P.ptau, p, np, per_instance, cfg.dv + 1) : upload(P.ptau, p, np * (cfg.dv + 1), per_instance, 0);
-  }
-  int init_u0(const void* u0, int per_instance) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (!u0) return fail(CGMRES_HIP_EINVAL, "init_u0: null pointer");
-    return upload(P.U, u0, nu, per_instance, cfg.dv);
-  }
-  int init_u0_newton(void* u0, const void* x0, const void* p0, int n_loop) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (!u0 || !x0 || (np && !p0)) return fail(CGMRES_HIP_EINVAL, "init_u0_newton: null pointer");
-    if (n_loop < 0) return fail(CGMRES_HIP_EINVAL, "init_u0_newton: n_loop < 0");
-    const size_t B = cfg.batch;
-    if (int rc = grow(&stage_b, &stage_b_n, B * (nu + nx + np))) return rc;
-    T *du = stage_b, *dx = du + B * nu, *dp = dx + B * nx;
-    HIP_TRY(hipMemcpyAsync(du, u0, B * nu * sizeof(T), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(dx, x0, B * nx * sizeof(T), hipMemcpyHostToDevice, stream));
-    if (np) HIP_TRY(hipMemcpyAsync(dp, p0, B * np * sizeof(T), hipMemcpyHostToDevice, stream));
-    newton_u0_kernel<M, T><<<dim3((B + 63) / 64), 64, 0, stream>>>(du, dx, dp, cfg.batch, n_loop);
-    HIP_TRY(hipGetLastError());
+  size_t pitch_U() const { return ldb; }
+  int spread_u0(const T* du) {
     dim3 grid((cfg.batch + 255) / 256, nu * cfg.dv);
-    replicate_stages<T><<<grid, 256, 0, stream>>>(P.U, du, cfg.batch, ldb, nu, cfg.dv, 0);  // cgmres.hpp:75
+    replicate_stages<T><<<grid, 256, 0, stream>>>(P.U, du, cfg.batch, ldb, nu, cfg.dv, 0);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(u0, du, B * nu * sizeof(T), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
     return 0;
   }
 
@@ -112,23 +84,7 @@ struct CtxLane final : cgmres_hip_ctx {
     t = t + P.dt;  // cgmres.hpp:107
     return 0;
   }
-  int control_device(void* u, const void* x, void* x_next) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (!u || !x) return fail(CGMRES_HIP_EINVAL, "control: null pointer");
-    return launch_tick(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x_next));
-  }
-  int control_host(void* u, const void* x) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (!u || !x) return fail(CGMRES_HIP_EINVAL, "control: null pointer");
-    HIP_TRY(hipMemcpyAsync(x_dev, x, size_t(cfg.batch) * nx * sizeof(T), hipMemcpyHostToDevice, stream));
-    if (int rc = launch_tick(u_dev, x_dev, nullptr)) return rc;
-    HIP_TRY(hipMemcpyAsync(u, u_dev, size_t(cfg.batch) * nu * sizeof(T), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
-  }
   int closed_loop(void* x, void* u, int n_ticks, const LoopSeqs& sq) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (!u || !x) return fail(CGMRES_HIP_EINVAL, "closed_loop: null pointer");
     const int all = np * (cfg.dv + 1), per_instance = sq.ptau_per_instance;
     const size_t per_tick = size_t(per_instance ? cfg.batch : 1) * all;
     // plant inputs (cgmres_hip_closed_loop_device_ex): d and v, [n_ticks][batch or 1][nx]
@@ -151,31 +107,20 @@ struct CtxLane final : cgmres_hip_ctx {
     return rc;
   }
 
-  double time() const override { return double(t); }
   int get_state(double* tt, void* U, void* dUdt) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     if (tt) *tt = double(t);
     if (int rc = download(U, P.U, L)) return rc;
     return download(dUdt, P.dUdt, L);
   }
   int set_state(double tt, const void* U, const void* dUdt) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     t = T(tt);
     if (U)
-      if (int rc = upload(P.U, U, L, 1, 0)) return rc;
+      if (int rc = upload(P.U, ldb, U, L, 0, 1)) return rc;
     if (dUdt)
-      if (int rc = upload(P.dUdt, dUdt, L, 1, 0)) return rc;
-    return 0;
-  }
-  int get_status(int32_t* n_ax, int32_t* reason) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (n_ax) HIP_TRY(hipMemcpyAsync(n_ax, P.n_ax, size_t(cfg.batch) * 4, hipMemcpyDeviceToHost, stream));
-    if (reason) HIP_TRY(hipMemcpyAsync(reason, P.reason, size_t(cfg.batch) * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+      if (int rc = upload(P.dUdt, ldb, dUdt, L, 0, 1)) return rc;
     return 0;
   }
   int get_krylov(void* V, void* H, void* rho, void* g) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     const int k1 = cfg.k_max + 1;
     int rc;
     if ((rc = download(V, P.V, L * k1)) || (rc = download(H, P.H, k1 * k1)) || (rc = download(rho, P.rho, k1)) ||
@@ -186,11 +131,10 @@ struct CtxLane final : cgmres_hip_ctx {
 
   // ---- white-box hooks -------------------------------------------------------------------------
   int hook_F(void* ret, const void* U, const void* x, double tt) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     const size_t ld = ldb;
-    if (int rc = grow(&stage_b, &stage_b_n, 2 * size_t(L) * ld)) return rc;
-    T *Uem = stage_b, *Rem = stage_b + size_t(L) * ld;
-    if (int rc = upload(Uem, U, L, 1, 0)) return rc;
+    if (int rc = grow(&stage2, &stage2_n, 2 * size_t(L) * ld)) return rc;
+    T *Uem = stage2, *Rem = stage2 + size_t(L) * ld;
+    if (int rc = upload(Uem, ldb, U, L, 0, 1)) return rc;
     HIP_TRY(hipMemcpyAsync(x_dev, x, size_t(cfg.batch) * nx * sizeof(T), hipMemcpyHostToDevice, stream));
     P.x_in = x_dev;
     hook_F_kernel<M, T><<<lane_grid(), 64, 0, stream>>>(P, Uem, Rem, dtau_of(T(tt)));
@@ -198,7 +142,6 @@ struct CtxLane final : cgmres_hip_ctx {
     return download(ret, Rem, L);
   }
   int hook_prepare(void* b, const void* x) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     HIP_TRY(hipMemcpyAsync(x_dev, x, size_t(cfg.batch) * nx * sizeof(T), hipMemcpyHostToDevice, stream));
     P.x_in = x_dev;
     P.dtau_h = dtau_of(t + P.h);
@@ -208,23 +151,21 @@ struct CtxLane final : cgmres_hip_ctx {
     return download(b, P.bvec, L);
   }
   int hook_Ax(void* out, const void* v) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     const size_t ld = ldb;
-    if (int rc = grow(&stage_b, &stage_b_n, 2 * size_t(L) * ld)) return rc;
-    T *Vem = stage_b, *Oem = stage_b + size_t(L) * ld;
-    if (int rc = upload(Vem, v, L, 1, 0)) return rc;
+    if (int rc = grow(&stage2, &stage2_n, 2 * size_t(L) * ld)) return rc;
+    T *Vem = stage2, *Oem = stage2 + size_t(L) * ld;
+    if (int rc = upload(Vem, ldb, v, L, 0, 1)) return rc;
     P.dtau_h = dtau_of(t + P.h);
     hook_Ax_kernel<M, T><<<lane_grid(), 64, 0, stream>>>(P, Vem, Oem);
     HIP_TRY(hipGetLastError());
     return download(out, Oem, L);
   }
   int hook_gmres(void* x, const void* b) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     const size_t ld = ldb;
-    if (int rc = grow(&stage_b, &stage_b_n, 2 * size_t(L) * ld)) return rc;
-    T *Xem = stage_b, *Bem = stage_b + size_t(L) * ld;
-    if (int rc = upload(Xem, x, L, 1, 0)) return rc;
-    if (int rc = upload(Bem, b, L, 1, 0)) return rc;
+    if (int rc = grow(&stage2, &stage2_n, 2 * size_t(L) * ld)) return rc;
+    T *Xem = stage2, *Bem = stage2 + size_t(L) * ld;
+    if (int rc = upload(Xem, ldb, x, L, 0, 1)) return rc;
+    if (int rc = upload(Bem, ldb, b, L, 0, 1)) return rc;
     P.dtau_h = dtau_of(t + P.h);
     hook_gmres_kernel<M, T><<<lane_grid(), 64, 0, stream>>>(P, Xem, Bem);
     HIP_TRY(hipGetLastError());

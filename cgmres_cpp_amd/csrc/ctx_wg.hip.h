@@ -7,7 +7,7 @@
 #include "tick_wave.hip.h"
 #include "tick_wg.hip.h"
 #include "wg_plan.hip.h"
-#include "util_kernels.hip.h"
+#include "ctx_host.hip.h"
 
 namespace cgm {
 
@@ -21,16 +21,15 @@ __global__ void replicate_rows_im(T* __restrict__ dst, size_t dst_pitch, const T
 }
 
 template <class M, class T>
-struct CtxWg final : cgmres_hip_ctx {
+struct CtxWg final : CtxHost<M, T, CtxWg<M, T>> {
+  using Host = CtxHost<M, T, CtxWg<M, T>>;
+  using Host::cfg, Host::nx, Host::nu, Host::np, Host::L, Host::stream, Host::dalloc, Host::grow, Host::init_common;
+  using Host::t, Host::dtau_of, Host::stage, Host::stage_n, Host::stage2, Host::stage2_n, Host::x_dev, Host::u_dev;
   WgParams<T> P{};
-  T t = T(0);
   int ks_all = 0;
   WgPlanResult plan{};  // what plan_wg (wg_plan.hip.h) decided for this batch
   void (*k_tick)(WgParams<T>) = nullptr;
   void (*k_hook)(WgParams<T>) = nullptr;
-  T *stage = nullptr, *stage2 = nullptr;
-  size_t stage_n = 0, stage2_n = 0;
-  T *x_dev = nullptr, *u_dev = nullptr;
   // control() through host pointers on a small batch (a single Cgmres<Model> object: batch 1): x and u travel through
   // host-mapped pinned buffers the kernel reads / writes directly — one launch + one stream synchronisation per tick
   // instead of copy, launch, copy, synchronise (each hipMemcpyAsync costs ~8 us of host time)
@@ -130,9 +129,6 @@ struct CtxWg final : cgmres_hip_ctx {
 
   dim3 grid() const { return dim3((cfg.batch + plan.k.ipw - 1) / plan.k.ipw); }
   dim3 block() const { return dim3(plan.k.ipw * 16); }
-  T dtau_of(T tt) const {  // cgmres.hpp:32-34, once per tick on the host for the whole batch
-    return T(cfg.Tf) * (1 - std::exp(-T(cfg.alpha) * tt)) / T(cfg.dv);
-  }
 
   // host [B][n] <-> device rows with pitch
   int rows_h2d(T* dst, size_t pitch, const void* src, int n) {
@@ -148,44 +144,21 @@ struct CtxWg final : cgmres_hip_ctx {
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
   }
-  int replicate(T* dst, size_t pitch, const void* src, int n, int reps, int per_instance) {
+  // host [B or 1][n] -> device rows with pitch, every row's n values repeated reps times (0: once)
+  int upload(T* dst, size_t pitch, const void* src, int n, int reps, int per_instance) {
     const size_t cnt = size_t(per_instance ? cfg.batch : 1) * n;
     if (int rc = grow(&stage, &stage_n, cnt)) return rc;
     HIP_TRY(hipMemcpyAsync(stage, src, cnt * sizeof(T), hipMemcpyHostToDevice, stream));
-    replicate_rows_im<T><<<dim3(4, cfg.batch), 256, 0, stream>>>(dst, pitch, stage, cfg.batch, n, reps, !per_instance);
+    replicate_rows_im<T><<<dim3(4, cfg.batch), 256, 0, stream>>>(dst, pitch, stage, cfg.batch, n, reps ? reps : 1, !per_instance);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
   }
 
-  int set_ptau(const void* p, int per_instance, bool repeat) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (np == 0) return 0;
-    if (!p) return fail(CGMRES_HIP_EINVAL, "set_ptau: null pointer");
-    const int all = np * (cfg.dv + 1);
-    return repeat ? replicate(P.ptau, all, p, np, cfg.dv + 1, per_instance) : replicate(P.ptau, all, p, all, 1, per_instance);
-  }
-  int init_u0(const void* u0, int per_instance) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (!u0) return fail(CGMRES_HIP_EINVAL, "init_u0: null pointer");
-    return replicate(P.U, P.Lg, u0, nu, cfg.dv, per_instance);
-  }
-  int init_u0_newton(void* u0, const void* x0, const void* p0, int n_loop) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (!u0 || !x0 || (np && !p0)) return fail(CGMRES_HIP_EINVAL, "init_u0_newton: null pointer");
-    if (n_loop < 0) return fail(CGMRES_HIP_EINVAL, "init_u0_newton: n_loop < 0");
-    const size_t B = cfg.batch;
-    if (int rc = grow(&stage2, &stage2_n, B * (nu + nx + np))) return rc;
-    T *du = stage2, *dx = du + B * nu, *dp = dx + B * nx;
-    HIP_TRY(hipMemcpyAsync(du, u0, B * nu * sizeof(T), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(dx, x0, B * nx * sizeof(T), hipMemcpyHostToDevice, stream));
-    if (np) HIP_TRY(hipMemcpyAsync(dp, p0, B * np * sizeof(T), hipMemcpyHostToDevice, stream));
-    newton_u0_kernel<M, T><<<dim3((B + 63) / 64), 64, 0, stream>>>(du, dx, dp, cfg.batch, n_loop);
+  size_t pitch_U() const { return P.Lg; }
+  int spread_u0(const T* du) {
+    replicate_rows_im<T><<<dim3(4, cfg.batch), 256, 0, stream>>>(P.U, P.Lg, du, cfg.batch, nu, cfg.dv, 0);
     HIP_TRY(hipGetLastError());
-    replicate_rows_im<T><<<dim3(4, cfg.batch), 256, 0, stream>>>(P.U, P.Lg, du, cfg.batch, nu, cfg.dv, 0);  // cgmres.hpp:75
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(u0, du, B * nu * sizeof(T), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
     return 0;
   }
 
@@ -209,11 +182,6 @@ struct CtxWg final : cgmres_hip_ctx {
     return 0;
   }
   int launch_tick(T* u_out, const T* x_in, T* x_next) { return launch_ticks(u_out, x_in, x_next, 1); }
-  int control_device(void* u, const void* x, void* x_next) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (!u || !x) return fail(CGMRES_HIP_EINVAL, "control: null pointer");
-    return launch_tick(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x_next));
-  }
   // all four members are set together or not at all: a failure half-way leaves no buffer behind
   int alloc_pinned(size_t bx, size_t bu) {
     void *hx = nullptr, *hu = nullptr, *dx = nullptr, *du = nullptr;
@@ -230,27 +198,17 @@ struct CtxWg final : cgmres_hip_ctx {
     return 0;
   }
   int control_host(void* u, const void* x) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (!u || !x) return fail(CGMRES_HIP_EINVAL, "control: null pointer");
-    if (cfg.batch <= kPinnedIoMaxBatch) {
-      const size_t bx = size_t(cfg.batch) * nx * sizeof(T), bu = size_t(cfg.batch) * nu * sizeof(T);
-      if (!pin_x)
-        if (int rc = alloc_pinned(bx, bu)) return rc;
-      std::memcpy(pin_x, x, bx);
-      if (int rc = launch_tick(pin_u_dev, pin_x_dev, nullptr)) return rc;
-      HIP_TRY(hipStreamSynchronize(stream));
-      std::memcpy(u, pin_u, bu);
-      return 0;
-    }
-    HIP_TRY(hipMemcpyAsync(x_dev, x, size_t(cfg.batch) * nx * sizeof(T), hipMemcpyHostToDevice, stream));
-    if (int rc = launch_tick(u_dev, x_dev, nullptr)) return rc;
-    HIP_TRY(hipMemcpyAsync(u, u_dev, size_t(cfg.batch) * nu * sizeof(T), hipMemcpyDeviceToHost, stream));
+    if (cfg.batch > kPinnedIoMaxBatch) return Host::control_host(u, x);  // the staged path
+    const size_t bx = size_t(cfg.batch) * nx * sizeof(T), bu = size_t(cfg.batch) * nu * sizeof(T);
+    if (!pin_x)
+      if (int rc = alloc_pinned(bx, bu)) return rc;
+    std::memcpy(pin_x, x, bx);
+    if (int rc = launch_tick(pin_u_dev, pin_x_dev, nullptr)) return rc;
     HIP_TRY(hipStreamSynchronize(stream));
+    std::memcpy(u, pin_u, bu);
     return 0;
   }
   int closed_loop(void* x, void* u, int n_ticks, const LoopSeqs& sq) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (!u || !x) return fail(CGMRES_HIP_EINVAL, "closed_loop: null pointer");
     const int all = np * (cfg.dv + 1), per_instance = sq.ptau_per_instance;
     const T* seq = all ? static_cast<const T*>(sq.ptau) : nullptr;
     const size_t per_tick = size_t(per_instance ? cfg.batch : 1) * all;
@@ -296,15 +254,12 @@ struct CtxWg final : cgmres_hip_ctx {
     return rc;
   }
 
-  double time() const override { return double(t); }
   int get_state(double* tt, void* U, void* dUdt) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     if (tt) *tt = double(t);
     if (int rc = rows_d2h(U, P.U, P.Lg, L, cfg.batch)) return rc;
     return rows_d2h(dUdt, P.dUdt, P.Lg, L, cfg.batch);
   }
   int set_state(double tt, const void* U, const void* dUdt) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     t = T(tt);
     if (U)
       if (int rc = rows_h2d(P.U, P.Lg, U, L)) return rc;
@@ -316,15 +271,7 @@ struct CtxWg final : cgmres_hip_ctx {
     *U = P.U, *dUdt = P.dUdt, *pitch = P.Lg;
     return 0;
   }
-  int get_status(int32_t* n_ax, int32_t* reason) override {
-    HIP_TRY(hipSetDevice(cfg.device));
-    if (n_ax) HIP_TRY(hipMemcpyAsync(n_ax, P.n_ax, size_t(cfg.batch) * 4, hipMemcpyDeviceToHost, stream));
-    if (reason) HIP_TRY(hipMemcpyAsync(reason, P.reason, size_t(cfg.batch) * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
-  }
   int get_krylov(void* V, void* H, void* rho, void* g) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     const int k1 = cfg.k_max + 1;
     if (V) {  // rows are pair-interleaved on the device (WgCtx::load_vec): element r + 16 m sits at (m/2)*32 + 2r + (m&1);
               // rows written by the row-parallel Newton kernel: element 12 r + i at (i/2)*32 + 2r + (i&1) (StageOwn)
@@ -373,19 +320,15 @@ struct CtxWg final : cgmres_hip_ctx {
     return 0;
   }
   int hook_F(void* ret, const void* U, const void* x, double tt) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     return run_hook(WG_HOOK_F, U, nullptr, ret, x, dtau_of(T(tt)));
   }
   int hook_prepare(void* b, const void* x) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     return run_hook(WG_HOOK_PREPARE, nullptr, nullptr, b, x, T(0));
   }
   int hook_Ax(void* out, const void* v) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     return run_hook(WG_HOOK_AX, v, nullptr, out, nullptr, T(0));
   }
   int hook_gmres(void* x, const void* b) override {
-    HIP_TRY(hipSetDevice(cfg.device));
     return run_hook(WG_HOOK_GMRES, x, b, x, nullptr, T(0));
   }
 };

@@ -5,7 +5,6 @@ same for tests/plan_probe_user.hip (user models: cfg.model_id is the index of an
 tests/user_models/shape_models.hpp); plan(), layout() and check_layout() work on either library."""
 import ctypes as C
 import os
-import subprocess
 
 import cgmres_cpp_amd as cg
 from cgmres_cpp_amd import build as B
@@ -29,27 +28,22 @@ USER_MODELS_HPP = os.path.join(HERE, "user_models", "shape_models.hpp")
 _libs = {}
 
 
-def _load(src, so, deps):
-    """The probe library of `src`, built on first use and rebuilt when a header or its source is newer."""
+def _load(src, so):
+    """The probe library of `src`, built on first use and rebuilt when its source or a file it includes is newer."""
     if so not in _libs:
-        _, hdrs = B.sources()
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in hdrs + [src] + deps):
-            os.makedirs(B.LIB_DIR, exist_ok=True)
-            r = subprocess.run([B.HIPCC] + B.CFLAGS + ["-shared", "-o", so, src], capture_output=True, text=True)
-            assert r.returncode == 0, r.stderr[-4000:]
-        _libs[so] = C.CDLL(so)
+        _libs[so] = C.CDLL(B.compile(so, src, ["-shared"]))
         _libs[so].lds_limit.restype = C.c_longlong
     return _libs[so]
 
 
 def probe():
     """The loaded probe library of the built-in models."""
-    return _load(PROBE_SRC, PROBE_SO, [])
+    return _load(PROBE_SRC, PROBE_SO)
 
 
 def probe_user():
     """The loaded probe library of the user models of tests/user_models/shape_models.hpp."""
-    return _load(USER_PROBE_SRC, USER_PROBE_SO, [USER_MODELS_HPP])
+    return _load(USER_PROBE_SRC, USER_PROBE_SO)
 
 
 def alias_info(lib, alias):

@@ -4,26 +4,18 @@ box) time bench.py against each through CGMRES_HIP_LIB.
     python tools/ab_build.py build name1:-DFLAG1 name2:-DFLAG2,-DFLAG3 ...
     python tools/ab_build.py bench name1 name2 ...      (prints ms_per_step per variant, interleaved rounds)"""
 import json, os, subprocess, sys
-from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from cgmres_cpp_amd import build as b
 AB = os.path.join(ROOT, "_ab")  # git-ignored, but travels with gpurun (gpurun_out/ does not)
 
-def build(name, flags, only=("capi.hip", "inst_pendulum_f64.hip")):
-    d = os.path.join(AB, name); os.makedirs(d, exist_ok=True)
-    srcs, _ = b.sources()
-    if os.environ.get("AB_SRC_ROOT"):  # another checkout of the sources (e.g. `git --work-tree=/tmp/old checkout HEAD -- cgmres_cpp_amd/csrc include`)
-        root = os.environ["AB_SRC_ROOT"]
-        srcs = [os.path.join(root, os.path.relpath(s, ROOT)) for s in srcs]
-        flags = flags + ["-I" + os.path.join(root, "include")]
-    def cc(s):
-        o = os.path.join(d, os.path.basename(s)[:-4] + ".o")
-        subprocess.run([b.HIPCC] + b.CFLAGS + flags + ["-c", "-o", o, s], check=True)
-        return o
-    with ThreadPoolExecutor(8) as ex:
-        objs = list(ex.map(cc, srcs))
-    subprocess.run([b.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fno-gpu-rdc", "-o", os.path.join(d, "lib.so")] + objs, check=True)
+def build(name, flags):
+    # AB_SRC_ROOT: another checkout of the sources (e.g. `git --work-tree=/tmp/old checkout HEAD -- cgmres_cpp_amd/csrc include`)
+    root = os.environ.get("AB_SRC_ROOT", ROOT)
+    d = os.path.join(AB, name)
+    # (force: the staleness rule knows neither the flags nor the source root an object was built with)
+    b.build(force=True, lib=os.path.join(d, "lib.so"), obj_dir=d, flags=flags + ["-I" + os.path.join(root, "include")],
+            csrc=os.path.join(root, os.path.relpath(b.CSRC, ROOT)))
 
 if sys.argv[1] == "build":
     for spec in sys.argv[2:]:

@@ -181,11 +181,12 @@ def blocks_main(sub, out_path):
 
 
 def operator_summary(header, cls):
-    from cgmres_cpp_amd.plugin import OP_TEMPLATE
+    from cgmres_cpp_amd.plugin import TEMPLATE
     os.makedirs(TMP, exist_ok=True)
     src = os.path.join(TMP, "op_" + re.sub(r"\W", "_", cls) + ".hip")
     with open(src, "w") as f:
-        f.write(OP_TEMPLATE.format(header=os.path.abspath(header), glue=os.path.join(CSRC, "user_operator.hip.h"), cls=cls))
+        f.write(TEMPLATE.format(origin=header, header=os.path.abspath(header), glue=os.path.join(CSRC, "user_operator.hip.h"),
+                                macro="CGMRES_HIP_DEFINE_OPERATOR", cls=cls))
     asm, rp = compile_tu(src)
     rm = remarks(rp)
     names = [m.group(1) for m in re.finditer(r"^(_Z\w+):", asm, re.M) if "gmres_" in m.group(1)]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic (never part of the product build): rebuilds the library with -DCGM_STAMPS into gpurun_out/diag/,
 runs closed-loop ticks at the headline size and prints where block 0 spends its shader cycles."""
-import ctypes, os, subprocess, sys
+import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
@@ -21,15 +21,8 @@ for a in sys.argv:
     if a.startswith("--lib="):  # a stamp build made earlier (e.g. an A/B pair copied aside)
         lib = os.path.abspath(a[6:])
 if "--build" in sys.argv or "--build-only" in sys.argv or not os.path.exists(lib):
-    srcs, _ = b.sources()
-    from concurrent.futures import ThreadPoolExecutor
-    def cc(s):
-        o = os.path.join(diag, os.path.basename(s)[:-4] + f"_{MODEL}.o")
-        subprocess.run([b.HIPCC] + b.CFLAGS + [a for a in sys.argv if a.startswith("-D")] + ["-DCGM_STAMPS", f"-DCGM_STAMPS_MODEL={MODEL_CODE}", "-c", "-o", o, s], check=True)
-        return o
-    with ThreadPoolExecutor(8) as ex:
-        objs = list(ex.map(cc, srcs))
-    subprocess.run([b.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fno-gpu-rdc", "-o", lib] + objs, check=True)
+    b.build(force="--build" in sys.argv or "--build-only" in sys.argv, lib=lib, obj_dir=os.path.join(diag, MODEL),
+            flags=[a for a in sys.argv if a.startswith("-D")] + ["-DCGM_STAMPS", f"-DCGM_STAMPS_MODEL={MODEL_CODE}"])
     if "--build-only" in sys.argv:
         sys.exit(0)
 b.LIB_PATH = lib
