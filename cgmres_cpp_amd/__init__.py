@@ -37,7 +37,7 @@ SYMBOLS = [
     "cgmres_hip_get_time", "cgmres_hip_get_state", "cgmres_hip_set_state", "cgmres_hip_get_status",
     "cgmres_hip_get_krylov", "cgmres_hip_F_func", "cgmres_hip_prepare", "cgmres_hip_Ax_func", "cgmres_hip_gmres",
     "cgmres_hip_timer_start", "cgmres_hip_timer_stop", "cgmres_hip_malloc", "cgmres_hip_free",
-    "cgmres_hip_memcpy_h2d", "cgmres_hip_memcpy_d2h", "cgmres_hip_state_rows",
+    "cgmres_hip_memcpy_h2d", "cgmres_hip_memcpy_d2h", "cgmres_hip_state_rows", "cgmres_hip_horizon_device",
 ]
 
 
@@ -54,6 +54,12 @@ class LoopInputs(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("ptau_per_instance", C.c_int32), ("dist_per_instance", C.c_int32),
                 ("meas_per_instance", C.c_int32), ("ptau_seq_dev", C.c_void_p), ("dist_seq_dev", C.c_void_p),
                 ("meas_seq_dev", C.c_void_p)]
+
+
+class Horizon(C.Structure):
+    """struct cgmres_hip_horizon_out (include/cgmres_hip.h): the device arrays cgmres_hip_horizon_device fills."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("xtau_dev", C.c_void_p), ("ltau_dev", C.c_void_p),
+                ("F_dev", C.c_void_p), ("fnorm_dev", C.c_void_p)]
 
 
 class CgmresHipError(RuntimeError):
@@ -120,6 +126,8 @@ def load():
     lib.cgmres_hip_free.argtypes = [vp, vp]
     lib.cgmres_hip_memcpy_h2d.argtypes = [vp, vp, vp, C.c_uint64]
     lib.cgmres_hip_memcpy_d2h.argtypes = [vp, vp, vp, C.c_uint64]
+    if hasattr(lib, "cgmres_hip_horizon_device"):  # (absent from A/B builds of older sources, tools/ab_build.py)
+        lib.cgmres_hip_horizon_device.argtypes = [vp, vp, C.POINTER(Horizon)]
     if hasattr(lib, "cgmres_hip_state_rows"):  # (absent from A/B builds of older sources, tools/ab_build.py)
         lib.cgmres_hip_state_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
     _lib = lib
@@ -418,6 +426,42 @@ class CgmresBatch:
 
     def synchronize(self):
         _check(load().cgmres_hip_synchronize(self._h))
+
+    # -- the predicted horizon and the optimality error, cgmres.hpp:113-162 ---------------------------
+    def horizon_device(self, x_dev, xtau=None, ltau=None, F=None, fnorm=None):
+        """F_func(ret, U, x, t) with the handle's current U, ptau and t at x_dev [batch, dim_x], on the stream (no copy, no
+        synchronise): fills the device arrays given — xtau, ltau [batch, dv+1, dim_x], F [batch, dim_u*dv], fnorm [batch] =
+        ||F|| — and leaves the controller state alone (cgmres_hip_horizon_device)."""
+        n_traj = self.batch * (self.dv + 1) * self.dim_x
+        out = Horizon(struct_size=C.sizeof(Horizon), reserved=0,
+                      xtau_dev=_ptr(xtau, self.np_dtype, n_traj), ltau_dev=_ptr(ltau, self.np_dtype, n_traj),
+                      F_dev=_ptr(F, self.np_dtype, self.batch * self.len), fnorm_dev=_ptr(fnorm, self.np_dtype, self.batch))
+        _check(load().cgmres_hip_horizon_device(self._h, _ptr(x_dev, self.np_dtype, self.batch * self.dim_x), C.byref(out)))
+
+    def _horizon_host(self, x, names):
+        xd = None
+        if isinstance(x, (DeviceBuffer, int)) or hasattr(x, "data_ptr"):
+            x_dev = x
+        else:
+            x_dev = xd = self.device_buffer((self.batch, self.dim_x)).upload(self._host(x, (self.batch, self.dim_x))[0])
+        shapes = {"xtau": (self.batch, self.dv + 1, self.dim_x), "ltau": (self.batch, self.dv + 1, self.dim_x),
+                  "F": (self.batch, self.len), "fnorm": (self.batch,)}
+        bufs = {k: self.device_buffer(shapes[k]) for k in names}
+        try:
+            self.horizon_device(x_dev, **bufs)
+            return tuple(bufs[k].download() for k in names)  # (memcpy_d2h is stream-ordered and blocks)
+        finally:
+            for b in list(bufs.values()) + ([xd] if xd is not None else []):
+                b.free()
+
+    def horizon(self, x):
+        """(xtau, ltau, F, fnorm) as numpy arrays for a host or device x [batch, dim_x]: what the controllers predict the
+        plant will do over the horizon, the costates, the optimality residual and its norm."""
+        return self._horizon_host(x, ("xtau", "ltau", "F", "fnorm"))
+
+    def opt_error(self, x):
+        """||F(U, x, t)|| per instance [batch]: the optimality error, the health figure of C/GMRES."""
+        return self._horizon_host(x, ("fnorm",))[0]
 
     # -- state ------------------------------------------------------------------------------------
     @property

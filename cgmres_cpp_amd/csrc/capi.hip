@@ -30,6 +30,7 @@ struct Plugin {
   cgmres_hip_ctx* (*make)(const cgmres_hip_config*);
   int (*probe)(const double*, const double*, const double*, const double*, double*, void*);
   const char* (*last_error)(void);
+  cgm::HorizonFn* horizon;  // optional symbol: null in a plugin built before cgmres_hip_horizon_device existed
 };
 std::deque<Plugin>& plugins() {  // deque: find_plugin hands out pointers that must survive later push_backs
   static std::deque<Plugin> v;
@@ -118,18 +119,20 @@ struct Builtin {
   using Dev = M<double>;
   cgmres_hip_ctx* (*make_f64)(const cgmres_hip_config&, int*);
   cgmres_hip_ctx* (*make_f32)(const cgmres_hip_config&, int*);
+  cgm::HorizonFn *horizon_f64, *horizon_f32;  // cgmres_hip_horizon_device on a context that factory made
 };
 template <class F>
 bool with_builtin(int id, F&& f) {
   switch (id) {
     case CGMRES_HIP_MODEL_PENDULUM:
-      f(Builtin<cgm::PendulumDev>{cgm::make_pendulum_f64, cgm::make_pendulum_f32});
+      f(Builtin<cgm::PendulumDev>{cgm::make_pendulum_f64, cgm::make_pendulum_f32, cgm::horizon_pendulum_f64, cgm::horizon_pendulum_f32});
       return true;
     case CGMRES_HIP_MODEL_MSD:
-      f(Builtin<cgm::MsdDev>{cgm::make_msd_f64, cgm::make_msd_f32});
+      f(Builtin<cgm::MsdDev>{cgm::make_msd_f64, cgm::make_msd_f32, cgm::horizon_msd_f64, cgm::horizon_msd_f32});
       return true;
     case CGMRES_HIP_MODEL_SEMIACTIVE:
-      f(Builtin<cgm::SemiactiveDev>{cgm::make_semiactive_f64, cgm::make_semiactive_f32});
+      f(Builtin<cgm::SemiactiveDev>{cgm::make_semiactive_f64, cgm::make_semiactive_f32, cgm::horizon_semiactive_f64,
+                                     cgm::horizon_semiactive_f32});
       return true;
   }
   return false;
@@ -286,7 +289,8 @@ int cgmres_hip_register_model(const char* plugin_path, int32_t* model_id) {
   int32_t n = 0;
   const int rc = open_plugin(
       plugins(), "model", "cgmres_hip_plugin_", plugin_path, model_id ? &n : nullptr, pl,
-      {{"info", &info, true}, {"make", &pl.make, true}, {"probe", &pl.probe, true}, {"last_error", &pl.last_error, true}},
+      {{"info", &info, true}, {"make", &pl.make, true}, {"probe", &pl.probe, true}, {"last_error", &pl.last_error, true},
+       {"horizon", &pl.horizon, false}},
       [&](Plugin& q) {
         int32_t dims[5];
         double tun[6];
@@ -482,6 +486,29 @@ int cgmres_hip_closed_loop_device_ex(cgmres_hip_handle h, void* x, void* u, int3
     sq.meas = in->meas_seq_dev, sq.meas_per_instance = in->meas_per_instance;
   }
   return closed_loop(h, x, u, n_ticks, sq);
+}
+int cgmres_hip_horizon_device(cgmres_hip_handle h, const void* x, const cgmres_hip_horizon_out* out) {
+  NEED(h);
+  if (!x) return fail(CGMRES_HIP_EINVAL, "horizon_device: null x_dev");
+  if (!out) return fail(CGMRES_HIP_EINVAL, "horizon_device: null out");
+  if (out->struct_size != int32_t(sizeof(cgmres_hip_horizon_out)))
+    return fail(CGMRES_HIP_EINVAL, "horizon_device: struct_size %d, this library's cgmres_hip_horizon_out has %d", out->struct_size,
+                int(sizeof(cgmres_hip_horizon_out)));
+  if (out->reserved != 0) return fail(CGMRES_HIP_EINVAL, "horizon_device: cgmres_hip_horizon_out.reserved must be 0 (got %d)", out->reserved);
+  if (!out->xtau_dev && !out->ltau_dev && !out->F_dev && !out->fnorm_dev)
+    return fail(CGMRES_HIP_EINVAL, "horizon_device: no output wanted (xtau_dev, ltau_dev, F_dev and fnorm_dev are all null)");
+  ENTER(h);
+  if (const Plugin* pl = find_plugin(h->cfg.model_id)) {  // user models: the plugin knows the context's concrete type
+    if (!pl->horizon)
+      return fail(CGMRES_HIP_EINVAL, "horizon_device: the plugin %s was built before this entry point existed: rebuild it",
+                  pl->path.c_str());
+    const int rc = pl->horizon(h, x, out);
+    if (rc) cgm::g_err = pl->last_error();  // (the plugin has its own copy of the error string)
+    return rc;
+  }
+  int rc = fail(CGMRES_HIP_EINVAL, "horizon_device: unknown model_id %d", h->cfg.model_id);
+  with_builtin(h->cfg.model_id, [&](auto m) { rc = (h->cfg.dtype == CGMRES_HIP_F32 ? m.horizon_f32 : m.horizon_f64)(h, x, out); });
+  return rc;
 }
 int cgmres_hip_shard_bounds(int32_t n, int32_t world, int32_t rank, int32_t* lo, int32_t* hi) {
   if (n < 0 || world < 1 || rank < 0 || rank >= world || !lo || !hi)

@@ -11,8 +11,10 @@
 //                                           repeated reps times (0: copied once, no repetition kernel)
 //   spread_u0(du)                           device [B][nu] -> P.U, repeated over the horizon
 //   pitch_U()                               what upload() takes as the pitch of P.U
+//   horizon_views(U, ptau, rows)            strided views of P.U and P.ptau for horizon(); *rows: instance-major rows
 #pragma once
 #include "ctx_common.hip.h"
+#include "horizon.hip.h"
 #include "util_kernels.hip.h"
 
 namespace cgm {
@@ -23,6 +25,8 @@ struct CtxHost : cgmres_hip_ctx {
   T *stage = nullptr, *stage2 = nullptr;  // device staging, grown on demand: upload(), and init_u0_newton / the hooks
   size_t stage_n = 0, stage2_n = 0;
   T *x_dev = nullptr, *u_dev = nullptr;  // [B][nx], [B][nu] staging for the host-pointer entry points
+  T* hz = nullptr;                       // scratch of horizon(), grown on demand
+  size_t hz_n = 0;
 
   D& self() { return static_cast<D&>(*this); }
 
@@ -63,6 +67,42 @@ struct CtxHost : cgmres_hip_ctx {
     if (int rc = self().launch_tick(u_dev, x_dev, nullptr)) return rc;
     HIP_TRY(hipMemcpyAsync(u, u_dev, size_t(cfg.batch) * nu * sizeof(T), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+  }
+
+  // cgmres_hip_horizon_device (horizon.hip.h): F_func(ret, U, x, t) of cgmres.hpp:113-162 with the handle's U, ptau and t,
+  // keeping xtau, ltau, F and ||F||; on the stream, no copy, no synchronise.  Not a virtual: the translation unit or plugin
+  // that made the context calls it on the concrete type (factory_impl.hip.h: horizon_variant).  Outputs the caller does
+  // not take and the costate sweep needs go to the scratch `hz`: element-major [n][ldh], like the lane mapping's arrays.
+  int horizon(const void* x, const cgmres_hip_horizon_out* o) {
+    constexpr HorizonPlan pl = horizon_plan_of<M, T>();
+    if (!pl.fits)
+      return fail(CGMRES_HIP_EINVAL, "horizon_device: one stage of this model (dim_x %d, dim_u %d, dim_p %d) exceeds the kernel's LDS",
+                  nx, nu, np);
+    const size_t ldh = size_t(cfg.batch + kHorizonLanes - 1) / kHorizonLanes * kHorizonLanes;
+    const size_t n_x = size_t(nx) * (cfg.dv + 1), n_t = size_t(M::NC) * cfg.dv, n_F = size_t(L);
+    const bool back = o->ltau_dev || o->F_dev || o->fnorm_dev;
+    const bool own_x = !o->xtau_dev, own_t = back && n_t, own_F = o->fnorm_dev && !o->F_dev;
+    if (int rc = grow(&hz, &hz_n, ((own_x ? n_x : 0) + (own_t ? n_t : 0) + (own_F ? n_F : 0)) * ldh)) return rc;
+    HorizonParams<T> H{};
+    H.B = cfg.batch, H.dv = cfg.dv, H.back = back;
+    H.dtau = dtau_of(t);  // cgmres.hpp:127
+    H.x = static_cast<const T*>(x);
+    int rows = 0;  // U and ptau are instance-major rows: the chunk loads run along the rows
+    self().horizon_views(&H.U, &H.ptau, &rows);
+    T* s = hz;
+    H.xtau = own_x ? HorizonView<T>{s, 1, ldh} : HorizonView<T>{static_cast<T*>(o->xtau_dev), n_x, 1};
+    if (own_x) s += n_x * ldh;
+    H.trig = own_t ? HorizonView<T>{s, 1, ldh} : HorizonView<T>{nullptr, 0, 0};
+    if (own_t) s += n_t * ldh;
+    H.F = own_F ? HorizonView<T>{s, 1, ldh} : HorizonView<T>{static_cast<T*>(o->F_dev), n_F, 1};
+    H.ltau = static_cast<T*>(o->ltau_dev), H.fnorm = static_cast<T*>(o->fnorm_dev);
+    const dim3 grid(unsigned(ldh / kHorizonLanes));
+    if (rows)
+      horizon_kernel<M, T, true><<<grid, kHorizonLanes, 0, stream>>>(H);
+    else
+      horizon_kernel<M, T, false><<<grid, kHorizonLanes, 0, stream>>>(H);
+    HIP_TRY(hipGetLastError());
     return 0;
   }
 

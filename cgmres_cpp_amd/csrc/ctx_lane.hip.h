@@ -68,6 +68,9 @@ struct CtxLane final : CtxHost<M, T, CtxLane<M, T>> {
   }
 
   size_t pitch_U() const { return ldb; }
+  void horizon_views(HorizonView<const T>* U, HorizonView<const T>* ptau, int* rows) const {
+    *U = {P.U, 1, size_t(ldb)}, *ptau = {P.ptau, 1, size_t(ldb)}, *rows = 0;  // element-major
+  }
   int spread_u0(const T* du) {
     dim3 grid((cfg.batch + 255) / 256, nu * cfg.dv);
     replicate_stages<T><<<grid, 256, 0, stream>>>(P.U, du, cfg.batch, ldb, nu, cfg.dv, 0);

@@ -156,6 +156,9 @@ struct CtxWg final : CtxHost<M, T, CtxWg<M, T>> {
   }
 
   size_t pitch_U() const { return P.Lg; }
+  void horizon_views(HorizonView<const T>* U, HorizonView<const T>* ptau, int* rows) const {
+    *U = {P.U, size_t(P.Lg), 1}, *ptau = {P.ptau, size_t(np) * (cfg.dv + 1), 1}, *rows = 1;  // instance-major rows
+  }
   int spread_u0(const T* du) {
     replicate_rows_im<T><<<dim3(4, cfg.batch), 256, 0, stream>>>(P.U, P.Lg, du, cfg.batch, nu, cfg.dv, 0);
     HIP_TRY(hipGetLastError());

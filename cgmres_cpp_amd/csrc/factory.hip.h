@@ -1,16 +1,21 @@
 // One factory per (model, scalar type): each lives in its own translation unit (inst_*.hip) so the kernel
 // instantiations compile in parallel.  Returns nullptr when the requested variant cannot serve the sizes;
 // *resolved receives the variant actually chosen (1 = lane, 2 = wg).
+// Next to each factory, what works on the concrete type of the context it made and is no virtual of cgmres_hip_ctx:
+// horizon_* = cgmres_hip_horizon_device (factory_impl.hip.h: horizon_variant), all six in inst_horizon.hip.
 #pragma once
 #include "ctx_common.hip.h"
 
 namespace cgm {
+using HorizonFn = int(cgmres_hip_ctx*, const void* x_dev, const cgmres_hip_horizon_out* out);
 cgmres_hip_ctx* make_pendulum_f64(const cgmres_hip_config& cfg, int* resolved);
 cgmres_hip_ctx* make_pendulum_f32(const cgmres_hip_config& cfg, int* resolved);
 cgmres_hip_ctx* make_msd_f64(const cgmres_hip_config& cfg, int* resolved);
 cgmres_hip_ctx* make_msd_f32(const cgmres_hip_config& cfg, int* resolved);
 cgmres_hip_ctx* make_semiactive_f64(const cgmres_hip_config& cfg, int* resolved);
 cgmres_hip_ctx* make_semiactive_f32(const cgmres_hip_config& cfg, int* resolved);
+HorizonFn horizon_pendulum_f64, horizon_pendulum_f32, horizon_msd_f64, horizon_msd_f32, horizon_semiactive_f64,
+    horizon_semiactive_f32;
 #ifdef CGM_STAMPS
 long long* debug_stamps_ptr();  // diagnostic build only: stamp buffer of the last pendulum/f64 wg context
 #endif

@@ -200,7 +200,19 @@ extern "C" int cgmres_hip_plugin_debug_lds_oob(void) {
 }
 #endif
 
-// The four entry points of a model plugin (bound by cgmres_hip_register_model in capi.hip).
+// The optional entry point of a model plugin: cgmres_hip_horizon_device on a context cgmres_hip_plugin_make made.  The
+// library refuses that call, and nothing else, for a plugin without the symbol — one built before it existed, which the
+// tests imitate with -DCGM_PLUGIN_WITHOUT_HORIZON.
+#ifdef CGM_PLUGIN_WITHOUT_HORIZON
+#define CGM_PLUGIN_HORIZON(MODEL)
+#else
+#define CGM_PLUGIN_HORIZON(MODEL)                                                                          \
+  int cgmres_hip_plugin_horizon(cgmres_hip_ctx* c, const void* x_dev, const cgmres_hip_horizon_out* out) { \
+    return cgm::horizon_variant<cgm::UserDev<MODEL>, double>(c, x_dev, out);                               \
+  }
+#endif
+
+// The entry points of a model plugin (bound by cgmres_hip_register_model in capi.hip): four required, horizon optional.
 #define CGMRES_HIP_DEFINE_PLUGIN(MODEL)                                                                          \
   extern "C" {                                                                                                   \
   int32_t cgmres_hip_plugin_abi(void) { return CGMRES_HIP_ABI_VERSION; }                                         \
@@ -234,4 +246,5 @@ extern "C" int cgmres_hip_plugin_debug_lds_oob(void) {
     return hipGetLastError() == hipSuccess ? 0 : -1;                                                             \
   }                                                                                                              \
   const char* cgmres_hip_plugin_last_error(void) { return cgm::g_err.c_str(); }                                  \
+  CGM_PLUGIN_HORIZON(MODEL)                                                                                      \
   }

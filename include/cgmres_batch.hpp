@@ -71,6 +71,12 @@ class CgmresBatch {
   void closed_loop_device(double* x_dev, double* u_dev, int32_t n_ticks, const cgmres_hip_loop_inputs& in) {
     cgmres_detail::check(cgmres_hip_closed_loop_device_ex(handle_, x_dev, u_dev, n_ticks, &in), "closed_loop_device_ex");
   }
+  // what F_func builds (cgmres.hpp:113-162) with the controllers' current U, ptau and t at x_dev [batch][dim_x]: the
+  // predicted state and costate trajectories, F and ||F|| into the device arrays `out` names (null = not wanted;
+  // `out.struct_size` must be sizeof(cgmres_hip_horizon_out)).  Asynchronous on the handle's stream; changes no state
+  void horizon_device(const double* x_dev, const cgmres_hip_horizon_out& out) {
+    cgmres_detail::check(cgmres_hip_horizon_device(handle_, x_dev, &out), "horizon_device");
+  }
   void synchronize() { cgmres_detail::check(cgmres_hip_synchronize(handle_), "synchronize"); }
 
   // Arnoldi mat-vecs executed and exit reason (CGMRES_HIP_EXIT_*) per instance for the last tick

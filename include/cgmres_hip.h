@@ -226,6 +226,26 @@ typedef struct cgmres_hip_loop_inputs {
 } cgmres_hip_loop_inputs;
 int cgmres_hip_closed_loop_device_ex(cgmres_hip_handle h, void* x_dev, void* u_dev, int32_t n_ticks,
                                      const cgmres_hip_loop_inputs* in);
+/* ---- the predicted horizon and the optimality error: what F_func builds, cgmres.hpp:113-162 ----------------------- */
+/* Evaluates F_func(ret, U, x, t) of the reference with the handle's CURRENT U, ptau and t (after a closed loop with a ptau
+ * sequence: the last tick's ptau) at the caller's x_dev [batch][dim_x], and keeps what a tick throws away: the predicted
+ * state trajectory xtau, the costate trajectory ltau, the optimality residual F and its norm, the health figure of
+ * C/GMRES.  Scalars in the handle's dtype, device pointers, instance-major like every other vector.  A NULL output pointer
+ * means that output is not wanted.  Stream-ordered on the handle's stream and asynchronous: no host copy, no synchronise,
+ * so it follows a cgmres_hip_closed_loop_device on the stream.  It changes nothing a later tick reads (t, U, dUdt, x_dxh,
+ * F_dxh_h, the Krylov arrays, the status).  Every mapping, both dtypes, every size cgmres_hip_create accepts.
+ * CGMRES_HIP_EINVAL, each with its own text: x_dev NULL, out NULL, a struct_size other than
+ * sizeof(cgmres_hip_horizon_out), a non-zero reserved, all four outputs NULL; a user model whose plugin was built before
+ * this entry point existed (rebuild the plugin: everything else of it keeps working). */
+typedef struct cgmres_hip_horizon_out {
+  int32_t struct_size;   /* sizeof(cgmres_hip_horizon_out); anything else: CGMRES_HIP_EINVAL */
+  int32_t reserved;      /* 0; anything else: CGMRES_HIP_EINVAL */
+  void* xtau_dev;        /* [batch][dv+1][dim_x]  cgmres.hpp:132-140 */
+  void* ltau_dev;        /* [batch][dv+1][dim_x]  cgmres.hpp:145-153 */
+  void* F_dev;           /* [batch][dim_u*dv]     cgmres.hpp:156-161 */
+  void* fnorm_dev;       /* [batch]               sqrt(sum_e F[e]^2), e ascending, accumulated in the handle's scalar type */
+} cgmres_hip_horizon_out;
+int cgmres_hip_horizon_device(cgmres_hip_handle h, const void* x_dev, const cgmres_hip_horizon_out* out);
 int cgmres_hip_synchronize(cgmres_hip_handle h);
 
 /* ---- state: the private members of Cgmres (cgmres.hpp:195-202) and Gmres (gmres.hpp:120-124) ------ */
