@@ -216,25 +216,20 @@ __device__ __forceinline__ int gmres_lane_core(int L, int kmax, T tol, size_t ld
     }
     for (int i = 0; i < k; ++i) {  // :71-77 stored reflectors
       const T g0 = g[size_t(3 * i) * ld], g1 = g[size_t(3 * i + 1) * ld], g2 = g[size_t(3 * i + 2) * ld];
-      const T a = Hk[size_t(i) * ld], c = Hk[size_t(i + 1) * ld];
-      const T beta = (g0 * a + g1 * c) * g2;
-      Hk[size_t(i) * ld] = a - beta * g0;
-      Hk[size_t(i + 1) * ld] = c - beta * g1;
+      const ReflectorApply<T> p(g0, g1, g2, Hk[size_t(i) * ld], Hk[size_t(i + 1) * ld]);
+      Hk[size_t(i) * ld] = p.first();
+      Hk[size_t(i + 1) * ld] = p.second();
     }
     {  // :78-90 new reflector and residual rotation
-      const T a = Hk[size_t(k) * ld], c = Hk[size_t(k + 1) * ld];
-      const T sigma = -(a < T(0.0) ? T(-1.0) : T(1.0)) * sqrt_t<T>(a * a + c * c);
-      const T g0 = a - sigma, g1 = c;
-      const T g2 = T(2.0) / (g0 * g0 + g1 * g1);
-      g[size_t(3 * k) * ld] = g0;
-      g[size_t(3 * k + 1) * ld] = g1;
-      g[size_t(3 * k + 2) * ld] = g2;
-      Hk[size_t(k) * ld] = sigma;
+      const Reflector<T> q = reflector_make(Hk[size_t(k) * ld], Hk[size_t(k + 1) * ld]);
+      g[size_t(3 * k) * ld] = q.g0;
+      g[size_t(3 * k + 1) * ld] = q.g1;
+      g[size_t(3 * k + 2) * ld] = q.g2;
+      Hk[size_t(k) * ld] = q.sigma;
       Hk[size_t(k + 1) * ld] = T(0.0);
-      const T ek = rho[size_t(k) * ld];
-      const T beta = g0 * ek * g2;
-      rho[size_t(k) * ld] = ek - beta * g0;
-      const T en = -beta * g1;
+      const ResidualRotate<T> e(q.g0, q.g1, q.g2, rho[size_t(k) * ld]);
+      rho[size_t(k) * ld] = e.first();
+      const T en = e.second();
       rho[size_t(k + 1) * ld] = en;
       if (abs_t(en) < tol) {  // :93-95, k not incremented
         reason = 1;

@@ -584,15 +584,15 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(VLDS ?
       for (int i = 0; i < K; ++i) {
         const T c = hc[i + 1];
         const T q0 = wave_bcast(gr0, i), q1 = wave_bcast(gr1, i), q2 = wave_bcast(gr2, i);
-        const T beta = (q0 * a + q1 * c) * q2;
-        hrot = lane == i ? a - beta * q0 : hrot;
-        a = c - beta * q1;
+        const ReflectorApply<T> p(q0, q1, q2, a, c);
+        hrot = lane == i ? p.first() : hrot;
+        a = p.second();
       }
-      const T sigma = -(a < T(0.0) ? T(-1.0) : T(1.0)) * sqrt_t<T>(a * a + hn * hn);
-      const T g0 = a - sigma, g1 = hn;
-      const T g2 = T(2.0) / (g0 * g0 + g1 * g1);
+      const Reflector<T> q = reflector_make(a, hn);
+      const T g0 = q.g0, g1 = q.g1, g2 = q.g2;
       gr0 = lane == K ? g0 : gr0, gr1 = lane == K ? g1 : gr1, gr2 = lane == K ? g2 : gr2;
-      hrot = lane == K ? sigma : hrot;
+      hrot = lane == K ? q.sigma : hrot;
+      // (the residual pair stays spelled out here: through ResidualRotate this kernel's code changes)
       const T beta = g0 * ek * g2;
       const T en = -beta * g1;
       e = lane == K ? ek - beta * g0 : (lane == K + 1 ? en : e);

@@ -96,27 +96,24 @@ __global__ __launch_bounds__(64) void gmres_op_kernel(int B, int ldb, int kmax, 
 // Everything of a solve stays in LDS (len (k_max + 3) + ~k_max^2/2 scalars, one len less in the row form: GmresWaveLds
 // of gmres_plan.hip.h): taken when that fits, the lane kernel serves the rest.  Sums associate as per-lane partial sums
 // + a reduction instead of index-ascending (rounding level).
+// (WgCtx::hess_column of wg_gmres.hip.h without its look-ahead loads: kept apart, merging them changes these kernels' code)
 template <class T>
 __device__ __forceinline__ T hess_column_lds(T* Hi, T* gi, T* rhoi, int k, T hn, bool writer) {  // gmres.hpp:71-90
   T* Hk = Hi + ((k * (k + 1)) >> 1);  // compact: column k = rows 0..k (h(k+1,k) arrives as `hn` and becomes 0)
   T a = Hk[0];
   for (int i = 0; i < k; ++i) {
-    const T g0 = gi[3 * i], g1 = gi[3 * i + 1], g2 = gi[3 * i + 2], c = Hk[i + 1];
-    const T beta = (g0 * a + g1 * c) * g2;
-    if (writer) Hk[i] = a - beta * g0;
-    a = c - beta * g1;
+    const T g0 = gi[3 * i], g1 = gi[3 * i + 1], g2 = gi[3 * i + 2];
+    const ReflectorApply<T> p(g0, g1, g2, a, Hk[i + 1]);
+    if (writer) Hk[i] = p.first();
+    a = p.second();
   }
-  const T c = hn;
-  const T sigma = -(a < T(0.0) ? T(-1.0) : T(1.0)) * sqrt_t<T>(a * a + c * c);
-  const T g0 = a - sigma, g1 = c;
-  const T g2 = T(2.0) / (g0 * g0 + g1 * g1);
-  const T ek = rhoi[k];
-  const T beta = g0 * ek * g2;
-  const T en = -beta * g1;
+  const Reflector<T> q = reflector_make(a, hn);
+  const ResidualRotate<T> e(q.g0, q.g1, q.g2, rhoi[k]);
+  const T en = e.second();
   if (writer) {
-    gi[3 * k] = g0, gi[3 * k + 1] = g1, gi[3 * k + 2] = g2;
-    Hk[k] = sigma;
-    rhoi[k] = ek - beta * g0;
+    gi[3 * k] = q.g0, gi[3 * k + 1] = q.g1, gi[3 * k + 2] = q.g2;
+    Hk[k] = q.sigma;
+    rhoi[k] = e.first();
     rhoi[k + 1] = en;
   }
   return en;

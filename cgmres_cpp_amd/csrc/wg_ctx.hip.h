@@ -330,6 +330,13 @@ struct WgCtx {
   // stage ownership (stage_own.hip.h; the so_* accessors)
   static constexpr int NV = StageOwn::NV;
   static_assert(!ROW_NEWTON || (SPL == StageOwn::SPL && M::NU == StageOwn::NU && IPW == 16), "stage_own.hip.h");
+  // the small Krylov arrays of this row's instance in LDS
+  struct Krylov {
+    T* H;    // compact: column k has k+1 entries (rows 0..k) at offset hoff(k); h(k+1,k): S.hsub
+    T* rho;  // the residual vector e, then y
+    T* g;    // reflector k: words 3k .. 3k+2
+  };
+  static __device__ __forceinline__ int hoff(int k) { return (k * (k + 1)) >> 1; }
 
   // ---- wg_sweep_serial.hip.h: the serial-sweep kernel's horizon sweep
   // F(U,x+hf,t+h) lives in HBM only (compiled out of the short-vector full-plan kernels)
@@ -456,6 +463,11 @@ struct WgCtx {
   // the clamped ring's rounds: pre(rows in flight), body(row, index), refill, post()
   template <bool SCHED, int DEPTH, class Body, class Pre, class Post>
   __device__ __forceinline__ void ring_walk(T (&buf)[DEPTH][NVEC], int first, int end, Body&& body, Pre&& pre, Post&& post) const;
+  // the steps of gmres() that stand alone (the others are regions of its frame, see there)
+  // lazy_qr: all Hessenberg columns behind the loop, one per lane of the row
+  __device__ __forceinline__ void qr_columns(Krylov K) const;
+  // y from the leading ks x ks block (gmres.hpp:100-107), in the form k_max selects; y -> K.rho
+  __device__ __forceinline__ void back_substitute(Krylov K, int ks) const;
   // Gmres::gmres around ax(): xv updated in place from b (bb) and A*x0 (ax0).  COLLECTIVE
   __device__ __forceinline__ void gmres(T* xv, const T* bb, const T* ax0);
   // status + small Krylov arrays of this row's instance -> HBM

@@ -19,21 +19,17 @@ __device__ __forceinline__ T CGM_WGCTX::hess_column(T* Hi, T* gi, T* rhoi, int k
   for (int i = 0; i < k; ++i) {
     const T g0 = g0n, g1 = g1n, g2 = g2n, c = cn;
     g0n = gi[3 * i + 3], g1n = gi[3 * i + 4], g2n = gi[3 * i + 5], cn = Hk[i + 2];
-    const T beta = (g0 * a + g1 * c) * g2;
-    if (writer) Hk[i] = a - beta * g0;
-    a = c - beta * g1;
+    const ReflectorApply<T> p(g0, g1, g2, a, c);
+    if (writer) Hk[i] = p.first();
+    a = p.second();
   }
-  const T c = hn;
-  const T sigma = -(a < T(0.0) ? T(-1.0) : T(1.0)) * sqrt_t<T>(a * a + c * c);
-  const T g0 = a - sigma, g1 = c;
-  const T g2 = T(2.0) / (g0 * g0 + g1 * g1);
-  const T ek = rhoi[k];
-  const T beta = g0 * ek * g2;
-  const T en = -beta * g1;
+  const Reflector<T> q = reflector_make(a, hn);
+  const ResidualRotate<T> e(q.g0, q.g1, q.g2, rhoi[k]);
+  const T en = e.second();
   if (writer) {
-    gi[3 * k] = g0, gi[3 * k + 1] = g1, gi[3 * k + 2] = g2;
-    Hk[k] = sigma;
-    rhoi[k] = ek - beta * g0;
+    gi[3 * k] = q.g0, gi[3 * k + 1] = q.g1, gi[3 * k + 2] = q.g2;
+    Hk[k] = q.sigma;
+    rhoi[k] = e.first();
     rhoi[k + 1] = en;
   }
   return en;
@@ -122,13 +118,104 @@ __device__ __forceinline__ void CGM_WGCTX::ring_walk(T (&buf)[DEPTH][NVEC], int 
     }
 }
 
+// gmres.hpp:71-90 for all columns at once (lazy_qr): lane c of the row owns column c and carries its running entry `a`
+// through the reflectors in order — step i: lane i turns (a, h(i+1,i)) into reflector i and leaves it in LDS, every
+// lane reads it back (same wave: LDS operations complete in order), the lanes c > i apply it to their column, and all
+// lanes advance the residual vector.  Per column the arithmetic and its order are those of hess_column; the serial
+// chain is k_max steps instead of k_max^2 / 2.
+CGM_WGCTX_T
+__device__ __forceinline__ void CGM_WGCTX::qr_columns(Krylov K) const {
+  const int kmax = P.kmax;
+  const int rs = S.reason[inst], nx = S.nax[inst];
+  const int n_col = !valid ? 0 : (rs == 0 ? nx : nx - 1);  // (a breakdown leaves its own column unrotated, :63-65)
+  const int c = r < kmax ? r : 0;
+  T* Hc = K.H + hoff(c);
+  const bool mine = r < n_col;
+  T a = mine ? Hc[0] : T(0);
+  T ek = K.rho[0];
+  for (int i = 0; i < kmax; ++i) {
+    if (!__any(i < n_col)) break;
+    const bool on = i < n_col;
+    const T cN = K.g[3 * i + 1];
+    const Reflector<T> q = reflector_make(a, cN);
+    if (on && r == i) {
+      K.g[3 * i] = q.g0, K.g[3 * i + 2] = q.g2;
+      Hc[i] = q.sigma;
+    }
+    const T g0 = K.g[3 * i], g1 = cN, g2 = K.g[3 * i + 2];
+    // (ResidualRotate and ReflectorApply of tick_common.hip.h, spelled out: through them the code of the two
+    // row-parallel kernels changes — profiles/wg_solver_steps_identity.md)
+    const T beta_r = g0 * ek * g2;
+    if (on && r == 0) K.rho[i] = ek - beta_r * g0;
+    ek = on ? -beta_r * g1 : ek;
+    if (mine && r > i) {
+      const T cn = Hc[i + 1];
+      const T beta = (g0 * a + g1 * cn) * g2;
+      Hc[i] = a - beta * g0;
+      a = cn - beta * g1;
+    }
+  }
+  if (r == 0 && n_col > 0) K.rho[n_col] = ek;
+}
+
+// Back substitution (gmres.hpp:100-107), column-oriented over the lanes of the row: lane j owns e_j; step i
+// (descending) turns e_i into y_i = e_i / H_ii, broadcasts it inside the row (ds_bpermute) and every lane j < i
+// subtracts H(j,i) y_i — for a fixed j the subtractions come in the reference's order (i = ks-1 ... j+1).
+// One LDS read + one crossbar round trip per step instead of a dependent LDS chain of length ks-i on lane 0.
+CGM_WGCTX_T
+__device__ __forceinline__ void CGM_WGCTX::back_substitute(Krylov K, int ks) const {
+  const int kmax = P.kmax;
+  T* const Hi = K.H;
+  T* const rhoi = K.rho;
+  if (kmax <= 15) {
+    T e = r < ks ? rhoi[r] : T(0);
+    const int row_lane0 = (threadIdx.x & 63) & ~15;
+    for (int i = ks - 1; i >= 0; --i) {
+      // (r > i + 1 reads words of the following columns / arrays: in bounds, only used where r < i)
+      const T hii = Hi[hoff(i) + i], hji = Hi[hoff(i) + r];
+      const T y = e / hii;                                   // meaningful in lane i
+      const T yi = row_bcast(y, row_lane0 + i);
+      e = r < i ? e - hji * yi : (r == i ? y : e);
+    }
+    if (r < ks) rhoi[r] = e;
+    if (r == 0) S.ksolve[inst] = ks;
+  } else if (kmax <= 31) {
+    // the same with TWO unknowns per lane (e_r and e_(r+16)): k_max = 20 of the long-horizon configuration — on lane 0
+    // alone the 200 dependent LDS steps of this solve were 2.7 % of that tick
+    T e0 = r < ks ? rhoi[r] : T(0), e1 = r + 16 < ks ? rhoi[r + 16] : T(0);
+    const int row_lane0 = (threadIdx.x & 63) & ~15;
+    for (int i = ks - 1; i >= 0; --i) {
+      // (rows beyond i + 1 read words of the following columns / arrays: in bounds, only used where the row is < i)
+      const T hii = Hi[hoff(i) + i], h0 = Hi[hoff(i) + r], h1 = Hi[hoff(i) + r + 16];
+      const bool hi_half = i >= 16;                           // (uniform) which of the lane's two unknowns e_i is
+      const T y = (hi_half ? e1 : e0) / hii;                  // meaningful in lane i & 15
+      const T yi = row_bcast(y, row_lane0 + (i & 15));
+      e0 = r < i ? e0 - h0 * yi : (r == i ? y : e0);
+      e1 = r + 16 < i ? e1 - h1 * yi : (r + 16 == i ? y : e1);
+    }
+    if (r < ks) rhoi[r] = e0;
+    if (r + 16 < ks) rhoi[r + 16] = e1;
+    if (r == 0) S.ksolve[inst] = ks;
+  } else if (r == 0) {
+    for (int i = ks - 1; i >= 0; --i) {
+      T ei = rhoi[i];
+      for (int j = ks - 1; j > i; --j) ei -= Hi[hoff(j) + i] * rhoi[j];
+      rhoi[i] = ei / Hi[hoff(i) + i];
+    }
+    S.ksolve[inst] = ks;
+  }
+}
+
 // Gmres::gmres (gmres.hpp:28-112).  In: x (registers `xv`), b (`bb`) and A*x0 (`ax0`), all in the row layout.
 // Out: xv updated.  All threads of the block must call this (it contains workgroup barriers).
+// The QR of all columns behind the loop and the back substitution are members (above).  The start, the iteration
+// gate, the mat-vec, the Gram-Schmidt rounds, the new basis row and the update of x are regions of this one frame, and
+// NBUF .. PARK its locals: as members, or with the constants in the class, every kernel's register allocation changed
+// (profiles/wg_solver_steps_identity.md has the trials), and the kernels are held to the code they had.
 CGM_WGCTX_T
 __device__ __forceinline__ void CGM_WGCTX::gmres(T* xv, const T* bb, const T* ax0) {
   const int kmax = P.kmax, k1 = kmax + 1;
   T* Hi = S.H + inst * P.Hp;  // compact: column k has k+1 entries (rows 0..k) at offset k(k+1)/2; h(k+1,k): S.hsub
-  auto hoff = [](int k) { return (k * (k + 1)) >> 1; };
   T* rhoi = S.rho + inst * k1;
   T* gi = S.g + inst * 3 * kmax;
   T vcur[NVEC], w[NVEC];
@@ -146,7 +233,7 @@ __device__ __forceinline__ void CGM_WGCTX::gmres(T* xv, const T* bb, const T* ax
   // needed until the Gram-Schmidt rounds).  Draining the look-ahead where the streaming loop ends keeps the ring path
   // free of both: s_waitcnt vmcnt(0), other counters untouched.
   auto drain_stream = [] {
-    if constexpr (!LEAN) __builtin_amdgcn_s_waitcnt(0x0F70);
+    if constexpr (!LEAN) __builtin_amdgcn_s_waitcnt(cgm_vmcnt_imm(0));
   };
   // The first NKEEP basis vectors never leave the row lanes' registers (the compiler parks them in the AGPR file): v_0
   // and v_1 are read again in every later iteration — 17 of the 55 Gram-Schmidt row reads of a k = 10 solve — and the
@@ -205,6 +292,7 @@ case n:            \
 #undef CGM_KCASE
   };
   static_assert(KRING == 12, "ring_cases has one case per basis length");
+  const Krylov K{Hi, rhoi, gi};  // for the steps that are members (qr_columns, back_substitute)
   auto no_stamp = [](auto...) {};
   // Diagnostic build: the Gram-Schmidt stamp split in three — 28 closes an explicit wait for the ring row a round is
   // about to use (the `younger` rows requested after it stay in flight, as in the product build), 29 the ring round
@@ -301,9 +389,7 @@ case n:            \
     } else {
     // Workgroup barrier that orders LDS only (W and the flags are what the sweep lanes need).  __syncthreads()
     // would also drain this wave's HBM store of the new basis row (s_waitcnt vmcnt(0)) — nobody else reads it.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    lds_barrier();
     {
       // (16-byte reads, all requested before the first is used: left as IPW scalar reads the compiler issued them as
       // eight ds_read2_b32 into ONE register pair, each behind s_waitcnt lgkmcnt(0) — eight LDS round trips in a row on
@@ -333,7 +419,7 @@ case n:            \
     // at most.  Together with drain_stream: state phase -0.8 k cycles per sweep, headline 134.2 -> 133.1 us/tick.)
     auto request_rows = [&]() {
       if (preload && active) {
-        __builtin_amdgcn_s_waitcnt(0x0F70);
+        __builtin_amdgcn_s_waitcnt(cgm_vmcnt_imm(0));
         if constexpr (COMPACT) ring_request(vbuf, NKEEP, k);
         else cases_request(vbuf, k);
       }
@@ -454,43 +540,7 @@ case n:            \
   }
   if constexpr (NWT == 0) __syncthreads();  // (NWT: the status words of a row are its own wave's)
   if constexpr (NWT != 0) {
-    if (lazy_qr) {
-      // gmres.hpp:71-90 for all columns at once: lane c of the row owns column c and carries its running entry `a`
-      // through the reflectors in order — step i: lane i turns (a, h(i+1,i)) into reflector i (the same expressions as
-      // hess_column) and leaves it in LDS, every lane reads it back (same wave: LDS operations complete in order),
-      // the lanes c > i apply it to their column, and all lanes advance the residual vector.  Per column the
-      // arithmetic and its order are those of hess_column; the serial chain is k_max steps instead of k_max^2 / 2.
-      const int rs = S.reason[inst], nx = S.nax[inst];
-      const int n_col = !valid ? 0 : (rs == 0 ? nx : nx - 1);  // (a breakdown leaves its own column unrotated, :63-65)
-      const int c = r < kmax ? r : 0;
-      T* Hc = Hi + hoff(c);
-      const bool mine = r < n_col;
-      T a = mine ? Hc[0] : T(0);
-      T ek = rhoi[0];
-      for (int i = 0; i < kmax; ++i) {
-        if (!__any(i < n_col)) break;
-        const bool on = i < n_col;
-        const T cN = gi[3 * i + 1];
-        const T sigma = -(a < T(0.0) ? T(-1.0) : T(1.0)) * sqrt_t<T>(a * a + cN * cN);
-        const T q0 = a - sigma;
-        const T q2 = T(2.0) / (q0 * q0 + cN * cN);
-        if (on && r == i) {
-          gi[3 * i] = q0, gi[3 * i + 2] = q2;
-          Hc[i] = sigma;
-        }
-        const T g0 = gi[3 * i], g1 = cN, g2 = gi[3 * i + 2];
-        const T beta_r = g0 * ek * g2;
-        if (on && r == 0) rhoi[i] = ek - beta_r * g0;
-        ek = on ? -beta_r * g1 : ek;
-        if (mine && r > i) {
-          const T cn = Hc[i + 1];
-          const T beta = (g0 * a + g1 * cn) * g2;
-          Hc[i] = a - beta * g0;
-          a = cn - beta * g1;
-        }
-      }
-      if (r == 0 && n_col > 0) rhoi[n_col] = ek;
-    }
+    if (lazy_qr) qr_columns(K);  // :71-90
   }
   CGM_STAMP(*this, 10);
   // natural exit: every column is used
@@ -502,49 +552,7 @@ case n:            \
     if constexpr (COMPACT) ring_request(vbx, NKEEP, ks);
     else cases_request(vbx, ks);
   }
-  if (valid && reason <= 1) {
-    // back substitution (gmres.hpp:100-107), column-oriented over the lanes of the row: lane j owns e_j; step i
-    // (descending) turns e_i into y_i = e_i / H_ii, broadcasts it inside the row (ds_bpermute) and every lane j < i
-    // subtracts H(j,i) y_i — for a fixed j the subtractions come in the reference's order (i = ks-1 ... j+1).
-    // One LDS read + one crossbar round trip per step instead of a dependent LDS chain of length ks-i on lane 0.
-    if (kmax <= 15) {
-      T e = r < ks ? rhoi[r] : T(0);
-      const int row_lane0 = (threadIdx.x & 63) & ~15;
-      for (int i = ks - 1; i >= 0; --i) {
-        // (r > i + 1 reads words of the following columns / arrays: in bounds, only used where r < i)
-        const T hii = Hi[hoff(i) + i], hji = Hi[hoff(i) + r];
-        const T y = e / hii;                                   // meaningful in lane i
-        const T yi = row_bcast(y, row_lane0 + i);
-        e = r < i ? e - hji * yi : (r == i ? y : e);
-      }
-      if (r < ks) rhoi[r] = e;
-      if (r == 0) S.ksolve[inst] = ks;
-    } else if (kmax <= 31) {
-      // the same with TWO unknowns per lane (e_r and e_(r+16)): k_max = 20 of the long-horizon configuration — on lane 0
-      // alone the 200 dependent LDS steps of this solve were 2.7 % of that tick
-      T e0 = r < ks ? rhoi[r] : T(0), e1 = r + 16 < ks ? rhoi[r + 16] : T(0);
-      const int row_lane0 = (threadIdx.x & 63) & ~15;
-      for (int i = ks - 1; i >= 0; --i) {
-        // (rows beyond i + 1 read words of the following columns / arrays: in bounds, only used where the row is < i)
-        const T hii = Hi[hoff(i) + i], h0 = Hi[hoff(i) + r], h1 = Hi[hoff(i) + r + 16];
-        const bool hi_half = i >= 16;                           // (uniform) which of the lane's two unknowns e_i is
-        const T y = (hi_half ? e1 : e0) / hii;                  // meaningful in lane i & 15
-        const T yi = row_bcast(y, row_lane0 + (i & 15));
-        e0 = r < i ? e0 - h0 * yi : (r == i ? y : e0);
-        e1 = r + 16 < i ? e1 - h1 * yi : (r + 16 == i ? y : e1);
-      }
-      if (r < ks) rhoi[r] = e0;
-      if (r + 16 < ks) rhoi[r + 16] = e1;
-      if (r == 0) S.ksolve[inst] = ks;
-    } else if (r == 0) {
-      for (int i = ks - 1; i >= 0; --i) {
-        T ei = rhoi[i];
-        for (int j = ks - 1; j > i; --j) ei -= Hi[hoff(j) + i] * rhoi[j];
-        rhoi[i] = ei / Hi[hoff(i) + i];
-      }
-      S.ksolve[inst] = ks;
-    }
-  }
+  if (valid && reason <= 1) back_substitute(K, ks);  // :100-107
   if constexpr (PARK) load_vec(xv, park_row);
   if constexpr (NWT == 0) __syncthreads();  // (NWT: y is written and read by the lanes of one row, i.e. one wave)
   CGM_STAMP(*this, 11);

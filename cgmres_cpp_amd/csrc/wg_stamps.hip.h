@@ -1,9 +1,13 @@
 // Diagnostic builds of the wg and wave tick kernels: the -DCGM_DEBUG_LDS flag word and the -DCGM_STAMPS phase clocks
-// (tools/phase_stamps.py).  Both compile to nothing in the product build.
+// (tools/phase_stamps.py).  Both compile to nothing in the product build; cgm_vmcnt_imm serves both builds.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace cgm {
+
+// s_waitcnt that leaves the `vm` youngest vector-memory operations in flight (gfx9 encoding: vmcnt in bits 3:0 and 15:14,
+// the other counters untouched)
+constexpr int cgm_vmcnt_imm(int vm) { return 0x0F70 | (vm & 15) | ((vm >> 4) << 14); }
 
 #ifdef CGM_DEBUG_LDS
 // Diagnostic build only: set by the costate sweep when one of its LDS addresses falls outside the workgroup's allocation
@@ -50,9 +54,6 @@ __device__ __forceinline__ void cgm_stamp_flush() {
     for (int i = 0; i < 2; ++i) g_cgm_stamps[60 + i] += acc[28 + i], g_cgm_stamps[62 + i] += acc[60 + i];
   }
 }
-// s_waitcnt that leaves the `vm` youngest vector-memory operations in flight (gfx9 encoding: vmcnt in bits 3:0 and 15:14,
-// the other counters untouched)
-constexpr int cgm_vmcnt_imm(int vm) { return 0x0F70 | (vm & 15) | ((vm >> 4) << 14); }
 #define CGM_STAMP(ctx, id) cgm_stamp(id)
 // the same behind the LDS operations in flight: what the stamp closes is a fetch, whose cost is the round trip and not the issue
 #define CGM_STAMP_LDS(ctx, id) (__extension__({ asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); cgm_stamp(id); }))
