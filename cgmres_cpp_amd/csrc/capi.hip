@@ -638,4 +638,16 @@ int cgmres_hip_debug_stamps(long long* out) {
 }
 #endif
 
+#ifdef CGM_AMAX
+/* diagnostic build only (tools/rot_increments.py): copies and clears the 16 words of cgm_amax_record (wg_stamps.hip.h) */
+int cgmres_hip_debug_amax(unsigned long long* out) {
+  unsigned long long* p = cgm::debug_amax_ptr();
+  if (!p || !out) return fail(CGMRES_HIP_EINVAL, "no increment buffer");
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, p, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemset(p, 0, 16 * sizeof(unsigned long long)));
+  return 0;
+}
+#endif
+
 }  // extern "C"

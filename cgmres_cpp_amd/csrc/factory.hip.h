@@ -19,4 +19,7 @@ HorizonFn horizon_pendulum_f64, horizon_pendulum_f32, horizon_msd_f64, horizon_m
 #ifdef CGM_STAMPS
 long long* debug_stamps_ptr();  // diagnostic build only: stamp buffer of the last pendulum/f64 wg context
 #endif
+#ifdef CGM_AMAX
+unsigned long long* debug_amax_ptr();  // diagnostic build only: rotation increments of the pendulum/f64 row-Newton kernel
+#endif
 }  // namespace cgm

@@ -11,4 +11,10 @@ long long* debug_stamps_ptr() {
   return hipGetSymbolAddress(&p, HIP_SYMBOL(g_cgm_stamps)) == hipSuccess ? static_cast<long long*>(p) : nullptr;
 }
 #endif
+#ifdef CGM_AMAX
+unsigned long long* debug_amax_ptr() {
+  void* p = nullptr;
+  return hipGetSymbolAddress(&p, HIP_SYMBOL(g_cgm_amax)) == hipSuccess ? static_cast<unsigned long long*>(p) : nullptr;
+}
+#endif
 }  // namespace cgm

@@ -13,6 +13,7 @@
 #include "stage_own.hip.h"
 #include "dpp.hip.h"
 #include "models.hip.h"
+#include "newton_rot.hip.h"
 #include "tick_common.hip.h"  // sqrt_t / FOut
 #include "wg_layout.hip.h"
 #include "wg_stamps.hip.h"
@@ -432,8 +433,9 @@ struct WgCtx {
   __device__ __forceinline__ void so_store_row(T* g, const T* reg) const;
   // first controls of U and of U + h d by stage, for the preamble's serial sweeps
   __device__ __forceinline__ void so_publish_u0(const T* d) const;
-  // sin / cos of (base angle + dl) from the base pair
-  __device__ __forceinline__ void rotate(T sb, T cb, T dl, T* sn_out, T* cs_out) const;
+  // sin dl and cos dl - 1 of a Newton increment (newton_rot.hip.h); (s, c) turned by the angle they belong to
+  static __device__ __forceinline__ void newton_rot_step(T dl, T* sn_out, T* cm1_out);
+  static __device__ __forceinline__ void turn(T* s, T* c, T sn, T cm1);
   // costate recurrence + dH/du of the row's instance from the owned stages' x and trig, in registers
   template <int MODE>
   __device__ __forceinline__ void row_costate(const T* x0f, const T* y1, const T* x2f, const T* y3, const T* sd, const T* cd,

@@ -62,4 +62,28 @@ __device__ __forceinline__ void cgm_stamp_flush() {
 #define CGM_STAMP_LDS(ctx, id) ((void)0)
 #endif
 
+#ifdef CGM_AMAX
+// Diagnostic build only (tools/rot_increments.py): the angle increments the row-Newton sweep hands to its rotation, per
+// wave and Newton iteration — words 0-7 for iteration 0 (the change of x0 under U + h v), 8-15 for the later ones (the
+// Newton correction): [0] the largest increment (bits of a non-negative double order as integers), [1] wave visits,
+// [2..6] visits with an increment above 2^-18, 2^-14, 2^-10, 2^-8, 2^-6.
+__device__ unsigned long long g_cgm_amax[16];
+__device__ __forceinline__ void cgm_amax_record(bool run, double amax, int it) {
+  unsigned long long* w = g_cgm_amax + (it == 0 ? 0 : 8);
+  const bool on = run && amax == amax;
+  const unsigned long long bits = (unsigned long long)__double_as_longlong(amax);
+  if (on && bits > w[0]) atomicMax(w, bits);
+  const bool a18 = __any(on && amax > 0x1p-18), a14 = __any(on && amax > 0x1p-14), a10 = __any(on && amax > 0x1p-10),
+             a8 = __any(on && amax > 0x1p-8), a6 = __any(on && amax > 0x1p-6), any = __any(on);
+  if ((threadIdx.x & 63) == 0 && any) {
+    atomicAdd(w + 1, 1ull);
+    if (a18) atomicAdd(w + 2, 1ull);
+    if (a14) atomicAdd(w + 3, 1ull);
+    if (a10) atomicAdd(w + 4, 1ull);
+    if (a8) atomicAdd(w + 5, 1ull);
+    if (a6) atomicAdd(w + 6, 1ull);
+  }
+}
+#endif
+
 }  // namespace cgm

@@ -138,20 +138,28 @@ __device__ __forceinline__ void CGM_WGCTX::so_publish_u0(const T* d) const {
     }
   }
 }
-// sin / cos of (base angle + dl) from the base pair, |dl| <= sqrt(rot_zmax)
+// The rotation of the Newton sweep's trig pairs, for the increments that sweep hands it (newton_rot.hip.h): sin dl and
+// cos dl - 1 from the short polynomials of |dl| <= 2^CGM_NEWTON_ROT_LOG2_R, and the turn of a pair (sin, cos) of a base
+// angle by the angle those two values belong to.  The turn by -dl takes (-sn, cm1) — the same bits as the polynomials
+// of -dl would give: z is even in dl and every other operation odd.
 CGM_WGCTX_T
-__device__ __forceinline__ void CGM_WGCTX::rotate(T sb, T cb, T dl, T* sn_out, T* cs_out) const {
-  constexpr int NRS = decltype(mc)::NRS, NRC = decltype(mc)::NRC;
+__device__ __forceinline__ void CGM_WGCTX::newton_rot_step(T dl, T* sn_out, T* cm1_out) {
+  constexpr double S[] = CGM_NEWTON_ROT_SIN, C[] = CGM_NEWTON_ROT_COS;
+  constexpr int NS = sizeof(S) / sizeof(S[0]), NC = sizeof(C) / sizeof(C[0]);
   const T z = dl * dl;
-  T ps = mc.rot_sin(NRS - 1), pc = mc.rot_cos(NRC - 1);
+  T ps = T(S[NS - 1]), pc = T(C[NC - 1]);
 #pragma unroll
-  for (int i = NRS - 2; i >= 0; --i) ps = fma_t(z, ps, mc.rot_sin(i));
+  for (int i = NS - 2; i >= 0; --i) ps = fma_t(z, ps, T(S[i]));
 #pragma unroll
-  for (int i = NRC - 2; i >= 0; --i) pc = fma_t(z, pc, mc.rot_cos(i));
-  const T sn = fma_t(z * dl, ps, dl);  // sin dl
-  const T cm1 = z * pc;                // cos dl - 1
-  *sn_out = sb + fma_t(sb, cm1, cb * sn);
-  *cs_out = cb + fma_t(cb, cm1, -(sb * sn));
+  for (int i = NC - 2; i >= 0; --i) pc = fma_t(z, pc, T(C[i]));
+  *sn_out = fma_t(z * dl, ps, dl);
+  *cm1_out = z * pc;
+}
+CGM_WGCTX_T
+__device__ __forceinline__ void CGM_WGCTX::turn(T* s, T* c, T sn, T cm1) {
+  const T sb = *s, cb = *c;
+  *s = sb + fma_t(sb, cm1, cb * sn);
+  *c = cb + fma_t(cb, cm1, -(sb * sn));
 }
 // Costate recurrence (cgmres.hpp:145-153) and dH/du (:156-161) of the row's instance from the states x(s) and trig
 // values of the owned stages (x of "stage dv" = the terminal state), in registers:
@@ -598,24 +606,31 @@ __device__ __forceinline__ void CGM_WGCTX::row_newton_sweep(T dtau, const T* v, 
     for (int q = 0; q < SPL; ++q)
       y3[q] = tr[q] ? ((q + 1 < SPL ? y1[q + 1 < SPL ? q + 1 : 0] : yb) - y1[q]) * inv_dtau_nb : T(0);
   }
-  T ad[SPL], a1[SPL];  // angle increments since the trig values were last brought up to date: of x0 - x1, of x1
+  // angle increment of x0 - x1 since the trig values were last brought up to date: the change of x0 in the first
+  // iteration, where x1 still is the base's, then minus the correction of x1 — whose own increment is that correction,
+  // so from the second iteration on one pair (sin, cos - 1) turns (sd, cd) one way and (s1, c1) the other
+  T ad[SPL];
 #pragma unroll
-  for (int q = 0; q < SPL; ++q) ad[q] = dx0[q], a1[q] = T(0);
-  const T rmax = T(0.9) * sqrt_t<T>(T(decltype(mc)::rot_zmax));
+  for (int q = 0; q < SPL; ++q) ad[q] = dx0[q];
+  const T rmax = T(1) / T(1ll << -(CGM_NEWTON_ROT_LOG2_R));
   for (int it = 0; it < NEWTON_MAX; ++it) {
     T jq[SPL], c0q[SPL], c1q[SPL];
     T amax = T(0);  // (stages outside the horizon carry harmless finite values)
 #pragma unroll
-    for (int q = 0; q < SPL; ++q) amax = __builtin_fmax(amax, __builtin_fmax(abs_t(ad[q]), abs_t(a1[q])));
+    for (int q = 0; q < SPL; ++q) amax = __builtin_fmax(amax, abs_t(ad[q]));
+#ifdef CGM_AMAX
+    cgm_amax_record(run, amax, it);
+#endif
     if (__builtin_expect((P.wave_dbg & 1) || __any(run && !(amax <= rmax)), 0)) {
 #pragma unroll
       for (int q = 0; q < SPL; ++q) mc.sincos_pair(x0f[q] - y1[q], y1[q], &sd[q], &cd[q], &s1[q], &c1[q]);
     } else {
 #pragma unroll
-      for (int q = 0; q < SPL; ++q) rotate(sd[q], cd[q], ad[q], &sd[q], &cd[q]);
-      if (it > 0) {
-#pragma unroll
-        for (int q = 0; q < SPL; ++q) rotate(s1[q], c1[q], a1[q], &s1[q], &c1[q]);
+      for (int q = 0; q < SPL; ++q) {
+        T sn, cm1;
+        newton_rot_step(ad[q], &sn, &cm1);
+        turn(&sd[q], &cd[q], sn, cm1);
+        if (it > 0) turn(&s1[q], &c1[q], -sn, cm1);
       }
     }
     // defects of the stage equations (the stage after the lane's last one belongs to the next lane) and the local
@@ -658,7 +673,7 @@ __device__ __forceinline__ void CGM_WGCTX::row_newton_sweep(T dtau, const T* v, 
 #pragma unroll
     for (int q = 0; q < SPL; ++q) {
       y1[q] += e1, y3[q] += e3;
-      dl1[q] = e1, ad[q] = -e1, a1[q] = e1;
+      dl1[q] = e1, ad[q] = -e1;
       // |e| - th (1 + |y|) > 0 ?  (the "- th" is taken off once, after the loop)
       const T vq = __builtin_fmax(fma_t(-th, abs_t(y1[q]), abs_t(e1)), fma_t(-th, abs_t(y3[q]), abs_t(e3)));
       viol = s_0 + q <= dv ? __builtin_fmax(viol, vq) : viol;  // (beyond stage dv its correction is carried on unchanged)

@@ -235,6 +235,10 @@ def main():
         i = args.index("--csrc")
         CSRC = os.path.abspath(args[i + 1])
         del args[i:i + 2]
+    for a in list(args):
+        if a.startswith("-D"):
+            EXTRA.append(a)
+            args.remove(a)
     if "--blocks" in args:
         i = args.index("--blocks")
         blocks_main(args[i + 1], out_path)
@@ -247,10 +251,6 @@ def main():
             open(os.path.join(ROOT, out_path) if not os.path.isabs(out_path) else out_path, "w").write(text)
         print(text)
         return
-    for a in list(args):
-        if a.startswith("-D"):
-            EXTRA.append(a)
-            args.remove(a)
     pat = args[0] if args else "tick_wg_kernel"
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.startswith("inst_") and f.endswith(".hip"))
     with ThreadPoolExecutor(min(6, len(os.sched_getaffinity(0)))) as ex:
