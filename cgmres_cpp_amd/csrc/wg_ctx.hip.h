@@ -313,6 +313,8 @@ struct WgCtx {
   static constexpr bool PAR_2PASS = PAR == 2 && PAR_OK;
   // row-parallel kernels (wg_sweep_rows.hip.h)
   static constexpr bool ROW_NEWTON = NWT == 1;
+  // its 16 lanes all store the words of the Hessenberg column that they all hold (mgs_round, gmres)
+  static constexpr bool ROW_ALL_STORE = ROW_NEWTON;
   // (Newton on an explicit recurrence cannot fail to terminate: iteration n makes stage n exact — its predecessor is —
   // so dv iterations reproduce the serial sweep whatever the start; the bound below is never reached by the test on the
   // correction, it only has to be >= dv.  Two iterations is what the mat-vecs of a tick take.)

@@ -6,6 +6,27 @@
 
 namespace cgm {
 
+// hn = sqrt(ss) and 1 / hn of the new basis row's squared norm from ONE reciprocal square root (row-Newton kernel): the
+// library's sqrt is 22 dependent instructions around v_rsq_f64 and the division behind it 14 more around v_rcp_f64,
+// all on the one chain every lane of the row waits for.  Here: the hardware's estimate y (about 2^-26 relative), one
+// coupled step on g = ss y -> sqrt and h = y / 2 -> 1 / (2 sqrt), two corrections of g from its own residual (the
+// library's steps, without its rescaling of arguments outside 2^+-767: ss is a squared norm of O(1) quantities, and a
+// value so small that the steps lose accuracy is far below the breakdown bound whatever they return), and one
+// correction of 2 h from the residual 1 - g (2 h).  Both values are within an ulp or two of the rounded ones (on the
+// bench: the same bits, profiles/r10_iter_diet_ab.json).  ss = 0 (the breakdown case: a direction the rounding of
+// U + h d absorbs) gives 0, a NaN or infinite ss a NaN — non-finite either way, as with sqrt.
+__device__ __forceinline__ void norm_and_inverse(double ss, double* hn, double* inv) {
+  const double y = __builtin_amdgcn_rsq(ss);
+  const double g0 = ss * y, h0 = 0.5 * y;
+  const double r0 = __builtin_fma(-h0, g0, 0.5);
+  const double g1 = __builtin_fma(g0, r0, g0), h1 = __builtin_fma(h0, r0, h0);
+  const double g2 = __builtin_fma(__builtin_fma(-g1, g1, ss), h1, g1);
+  const double g3 = __builtin_fma(__builtin_fma(-g2, g2, ss), h1, g2);
+  const double i1 = h1 + h1;
+  *inv = __builtin_fma(__builtin_fma(-g3, i1, 1.0), i1, i1);
+  *hn = ss > 0.0 ? g3 : ss;
+}
+
 // Hessenberg column k of one instance: stored reflectors, new reflector, residual rotation (gmres.hpp:71-90) — scalar
 // work on the instance's small Krylov arrays in LDS.  hn = h(k+1,k).  Returns rho_e[k+1]; `writer` lanes store.
 CGM_WGCTX_T
@@ -67,7 +88,9 @@ __device__ __forceinline__ void CGM_WGCTX::mgs_round(T* w, T* Hk, const T* vrow_
   const T hik = row16_sum(pa + pb);
 #pragma unroll
   for (int m = 0; m < NVEC; ++m) w[m] = w[m] - vi[m] * hik;
-  if (r == 0) Hk[i] = hik;
+  // (row-Newton kernel: all 16 lanes hold the same bits and store the same word — one store instead of a compare, an
+  // exec mask saved and restored around it, and the read of r back from the accumulator file)
+  if (ROW_ALL_STORE || r == 0) Hk[i] = hik;
 }
 // One term of x += V y (gmres.hpp:110-111): acc += v_j y_j
 CGM_WGCTX_T
@@ -488,8 +511,11 @@ case n:            \
         if (m + 1 < NVEC) nb += w[m + 1] * w[m + 1];
       }
       CGM_STAMP(*this, 7);
-      const T hn = sqrt_t<T>(row16_sum(na + nb));  // :60
-      if (r == 0) {
+      constexpr bool RSQ_NORM = ROW_NEWTON && std::is_same<T, double>::value;
+      T hn, inv_hn = T(0);  // :60, and :67 with it in the row-Newton kernel
+      if constexpr (RSQ_NORM) norm_and_inverse(row16_sum(na + nb), &hn, &inv_hn);
+      else hn = sqrt_t<T>(row16_sum(na + nb));
+      if (ROW_ALL_STORE || r == 0) {
         S.hsub[inst] = hn;
         S.nax[inst] = k + 1;
       }
@@ -500,7 +526,7 @@ case n:            \
           S.flag[inst] = 0;
         }
       } else {
-        const T inv = T(1.0) / hn;  // :67
+        const T inv = RSQ_NORM ? inv_hn : T(1.0) / hn;  // :67
 #pragma unroll
         for (int m = 0; m < NVEC; ++m) vcur[m] = w[m] * inv;
         store_vec(vrow(k + 1), vcur);
