@@ -22,6 +22,7 @@ EXIT_NATURAL, EXIT_CONVERGED, EXIT_SMALL_RESIDUAL, EXIT_BREAKDOWN, EXIT_NONFINIT
 FLAG_SERIAL_COSTATE, FLAG_IPW8, FLAG_NO_BINNING, FLAG_TWO_PASS_COSTATE = 1, 2, 4, 8
 FLAG_NO_WAVE, FLAG_WAVE_FRESH_TRIG, FLAG_WAVE_SERIAL_SWEEPS, FLAG_SERIAL_STATE_SWEEP = 16, 32, 64, 128
 ABI_VERSION = 3
+RECORD_BLOCK = 256  # CGMRES_HIP_RECORD_BLOCK: instances one workgroup of the record kernel covers per grid step
 TICKS_PER_LAUNCH = 10  # CGMRES_HIP_TICKS_PER_LAUNCH: closed_loop_device fuses this many ticks per launch (wg mapping)
 
 # every symbol include/cgmres_hip.h declares (tests/test_capi_symbols.py checks header == this == library)
@@ -38,6 +39,7 @@ SYMBOLS = [
     "cgmres_hip_get_krylov", "cgmres_hip_F_func", "cgmres_hip_prepare", "cgmres_hip_Ax_func", "cgmres_hip_gmres",
     "cgmres_hip_timer_start", "cgmres_hip_timer_stop", "cgmres_hip_malloc", "cgmres_hip_free",
     "cgmres_hip_memcpy_h2d", "cgmres_hip_memcpy_d2h", "cgmres_hip_state_rows", "cgmres_hip_horizon_device",
+    "cgmres_hip_ensemble_device", "cgmres_hip_closed_loop_device_rec", "cgmres_hip_record_plan",
 ]
 
 
@@ -60,6 +62,20 @@ class Horizon(C.Structure):
     """struct cgmres_hip_horizon_out (include/cgmres_hip.h): the device arrays cgmres_hip_horizon_device fills."""
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("xtau_dev", C.c_void_p), ("ltau_dev", C.c_void_p),
                 ("F_dev", C.c_void_p), ("fnorm_dev", C.c_void_p)]
+
+
+class EnsembleOut(C.Structure):
+    """struct cgmres_hip_ensemble_out (include/cgmres_hip.h): what cgmres_hip_ensemble_device fills."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("centre_dev", C.c_void_p), ("moments_dev", C.c_void_p),
+                ("counts_dev", C.c_void_p)]
+
+
+class LoopRecord(C.Structure):
+    """struct cgmres_hip_loop_record (include/cgmres_hip.h): the logs of cgmres_hip_closed_loop_device_rec."""
+    _fields_ = [("struct_size", C.c_int32), ("stride", C.c_int32), ("reserved", C.c_int32 * 2), ("x_log_dev", C.c_void_p),
+                ("u_log_dev", C.c_void_p), ("n_ax_log_dev", C.c_void_p), ("reason_log_dev", C.c_void_p),
+                ("t_host", C.c_void_p), ("centre_dev", C.c_void_p), ("moments_log_dev", C.c_void_p),
+                ("counts_log_dev", C.c_void_p)]
 
 
 class CgmresHipError(RuntimeError):
@@ -128,6 +144,10 @@ def load():
     lib.cgmres_hip_memcpy_d2h.argtypes = [vp, vp, vp, C.c_uint64]
     if hasattr(lib, "cgmres_hip_horizon_device"):  # (absent from A/B builds of older sources, tools/ab_build.py)
         lib.cgmres_hip_horizon_device.argtypes = [vp, vp, C.POINTER(Horizon)]
+    if hasattr(lib, "cgmres_hip_closed_loop_device_rec"):  # (absent from A/B builds of older sources, tools/ab_build.py)
+        lib.cgmres_hip_ensemble_device.argtypes = [vp, vp, vp, C.POINTER(EnsembleOut)]
+        lib.cgmres_hip_closed_loop_device_rec.argtypes = [vp, vp, vp, i32, C.POINTER(LoopInputs), C.POINTER(LoopRecord)]
+        lib.cgmres_hip_record_plan.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(i32)]
     if hasattr(lib, "cgmres_hip_state_rows"):  # (absent from A/B builds of older sources, tools/ab_build.py)
         lib.cgmres_hip_state_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
     _lib = lib
@@ -137,6 +157,16 @@ def load():
 def _check(rc):
     if rc != 0:
         raise CgmresHipError(f"cgmres_hip error {rc}: {load().cgmres_hip_last_error().decode()}")
+
+
+def record_plan(n_ticks, stride):
+    """cgmres_hip_record_plan: (n_rec, launch_ticks) — the records and the tick counts of the launches of a recorded closed
+    loop of n_ticks at `stride` on the mappings that fuse ticks.  No GPU."""
+    n_rec, n_l = C.c_int32(), C.c_int32()
+    _check(load().cgmres_hip_record_plan(int(n_ticks), int(stride), C.byref(n_rec), None, 0, C.byref(n_l)))
+    sizes = (C.c_int32 * max(1, n_l.value))()
+    _check(load().cgmres_hip_record_plan(int(n_ticks), int(stride), C.byref(n_rec), sizes, n_l.value, C.byref(n_l)))
+    return n_rec.value, list(sizes[:n_l.value])
 
 
 def device_count():
@@ -395,25 +425,8 @@ class CgmresBatch:
         _check(load().cgmres_hip_control_device(self._h, _ptr(u_dev, self.np_dtype, self.batch * self.dim_u),
                                                 _ptr(x_dev, self.np_dtype, self.batch * self.dim_x)))
 
-    def closed_loop_device(self, x_dev, u_dev, n_ticks, ptau_seq_dev=None, per_instance=True, *, dist_seq_dev=None,
-                           meas_seq_dev=None, dist_per_instance=True, meas_per_instance=True):
-        """n_ticks of the example main loop on the device.  ptau_seq_dev: optional device array of per-tick parameter
-        horizons, [n_ticks, batch, dim_p*(dv+1)] (per_instance) or [n_ticks, dim_p*(dv+1)] — `set_ptau` before every tick.
-        dist_seq_dev / meas_seq_dev: optional device arrays [n_ticks, batch, dim_x] (or [n_ticks, dim_x], broadcast) of a
-        process disturbance d and a measurement noise v: y_k = x_k + v_k, u_k = control(y_k),
-        x_{k+1} = (x_k + f(x_k, u_k)*dt) + d_k; x_dev holds the TRUE state (cgmres_hip_closed_loop_device_ex)."""
-        xp = _ptr(x_dev, self.np_dtype, self.batch * self.dim_x)
-        up = _ptr(u_dev, self.np_dtype, self.batch * self.dim_u)
-        if ptau_seq_dev is not None and self.dim_p == 0:
-            ptau_seq_dev = None
-        if dist_seq_dev is None and meas_seq_dev is None:
-            if ptau_seq_dev is None:
-                _check(load().cgmres_hip_closed_loop_device(self._h, xp, up, int(n_ticks)))
-            else:
-                n = int(n_ticks) * (self.batch if per_instance else 1) * self.dim_p * (self.dv + 1)
-                _check(load().cgmres_hip_closed_loop_device_ptau(self._h, xp, up, int(n_ticks),
-                                                                 _ptr(ptau_seq_dev, self.np_dtype, n), 1 if per_instance else 0))
-            return
+    def _loop_inputs(self, n_ticks, ptau_seq_dev, per_instance, dist_seq_dev, meas_seq_dev, dist_per_instance, meas_per_instance):
+        """struct cgmres_hip_loop_inputs of a call, element counts of typed buffers checked."""
         li = LoopInputs(struct_size=C.sizeof(LoopInputs), ptau_per_instance=1 if per_instance else 0,
                         dist_per_instance=1 if dist_per_instance else 0, meas_per_instance=1 if meas_per_instance else 0)
 
@@ -422,7 +435,109 @@ class CgmresBatch:
         li.ptau_seq_dev = _ptr(ptau_seq_dev, self.np_dtype, count(per_instance, self.dim_p * (self.dv + 1)))
         li.dist_seq_dev = _ptr(dist_seq_dev, self.np_dtype, count(dist_per_instance, self.dim_x))
         li.meas_seq_dev = _ptr(meas_seq_dev, self.np_dtype, count(meas_per_instance, self.dim_x))
+        return li
+
+    def closed_loop_device(self, x_dev, u_dev, n_ticks, ptau_seq_dev=None, per_instance=True, *, dist_seq_dev=None,
+                           meas_seq_dev=None, dist_per_instance=True, meas_per_instance=True, record=None):
+        """n_ticks of the example main loop on the device.  ptau_seq_dev: optional device array of per-tick parameter
+        horizons, [n_ticks, batch, dim_p*(dv+1)] (per_instance) or [n_ticks, dim_p*(dv+1)] — `set_ptau` before every tick.
+        dist_seq_dev / meas_seq_dev: optional device arrays [n_ticks, batch, dim_x] (or [n_ticks, dim_x], broadcast) of a
+        process disturbance d and a measurement noise v: y_k = x_k + v_k, u_k = control(y_k),
+        x_{k+1} = (x_k + f(x_k, u_k)*dt) + d_k; x_dev holds the TRUE state (cgmres_hip_closed_loop_device_ex).
+        record: a dict(stride=1, x=, u=, n_ax=, reason=, t=, centre=, moments=, counts=) of device buffers (t: a host float64
+        array), every one optional — every stride-th tick is recorded into them (cgmres_hip_closed_loop_device_rec)."""
+        xp = _ptr(x_dev, self.np_dtype, self.batch * self.dim_x)
+        up = _ptr(u_dev, self.np_dtype, self.batch * self.dim_u)
+        if ptau_seq_dev is not None and self.dim_p == 0:
+            ptau_seq_dev = None
+        if record is not None:
+            li = self._loop_inputs(n_ticks, ptau_seq_dev, per_instance, dist_seq_dev, meas_seq_dev, dist_per_instance,
+                                   meas_per_instance)
+            lr = self._loop_record(n_ticks, **record)
+            _check(load().cgmres_hip_closed_loop_device_rec(self._h, xp, up, int(n_ticks), C.byref(li), C.byref(lr)))
+            return
+        if dist_seq_dev is None and meas_seq_dev is None:
+            if ptau_seq_dev is None:
+                _check(load().cgmres_hip_closed_loop_device(self._h, xp, up, int(n_ticks)))
+            else:
+                n = int(n_ticks) * (self.batch if per_instance else 1) * self.dim_p * (self.dv + 1)
+                _check(load().cgmres_hip_closed_loop_device_ptau(self._h, xp, up, int(n_ticks),
+                                                                 _ptr(ptau_seq_dev, self.np_dtype, n), 1 if per_instance else 0))
+            return
+        li = self._loop_inputs(n_ticks, ptau_seq_dev, per_instance, dist_seq_dev, meas_seq_dev, dist_per_instance,
+                               meas_per_instance)
         _check(load().cgmres_hip_closed_loop_device_ex(self._h, xp, up, int(n_ticks), C.byref(li)))
+
+    # -- the record of a closed loop and the ensemble of a batch ----------------------------------------
+    def _loop_record(self, n_ticks, stride=1, x=None, u=None, n_ax=None, reason=None, t=None, centre=None, moments=None,
+                     counts=None):
+        """struct cgmres_hip_loop_record; typed buffers are checked for element type and count before their address
+        crosses the ABI (a stride < 1 or a negative n_ticks is the library's to refuse: nothing is checked then)."""
+        ok = int(stride) >= 1 and int(n_ticks) >= 0
+        n_rec = int(n_ticks) // int(stride) if ok else None
+        nc = self.dim_x + self.dim_u
+
+        def count(width):
+            return n_rec * width if ok else None
+        if t is not None and not (isinstance(t, np.ndarray) and t.dtype == np.float64):
+            raise TypeError("record t must be a host float64 numpy array")
+        return LoopRecord(struct_size=C.sizeof(LoopRecord), stride=int(stride),
+                          x_log_dev=_ptr(x, self.np_dtype, count(self.batch * self.dim_x)),
+                          u_log_dev=_ptr(u, self.np_dtype, count(self.batch * self.dim_u)),
+                          n_ax_log_dev=_ptr(n_ax, np.int32, count(self.batch)),
+                          reason_log_dev=_ptr(reason, np.int32, count(self.batch)),
+                          t_host=_ptr(t, np.float64, count(1)), centre_dev=_ptr(centre, np.float64, nc),
+                          moments_log_dev=_ptr(moments, np.float64, count(nc * 4)),
+                          counts_log_dev=_ptr(counts, np.int32, count(self.k_max + 7)))
+
+    def ensemble_device(self, x_dev, u_dev, moments=None, counts=None, centre=None):
+        """The statistics of one row of the batch on the stream (cgmres_hip_ensemble_device): moments [dim_x+dim_u, 4] =
+        {s1, s2, min, max} of double(value) - centre over the instances whose row is finite, counts [k_max+7] = histogram
+        of n_ax, instances per exit code, counting instances; float64 / int32 device buffers, centre [dim_x+dim_u] float64."""
+        nc = self.dim_x + self.dim_u
+        out = EnsembleOut(struct_size=C.sizeof(EnsembleOut), reserved=0, centre_dev=_ptr(centre, np.float64, nc),
+                          moments_dev=_ptr(moments, np.float64, nc * 4), counts_dev=_ptr(counts, np.int32, self.k_max + 7))
+        _check(load().cgmres_hip_ensemble_device(self._h, _ptr(x_dev, self.np_dtype, self.batch * self.dim_x),
+                                                 _ptr(u_dev, self.np_dtype, self.batch * self.dim_u), C.byref(out)))
+
+    def closed_loop_record(self, x, n_ticks, stride=1, centre=None, u=None, ptau_seq=None, per_instance=True, dist_seq=None,
+                           meas_seq=None, dist_per_instance=True, meas_per_instance=True):
+        """The convenience form: n_ticks of the device loop from the host state x [batch, dim_x], every stride-th tick
+        recorded; the sequences are host arrays.  Allocates, runs, synchronises and returns numpy arrays:
+        dict(t [n_rec], x [n_rec, batch, dim_x], u [n_rec, batch, dim_u], n_ax, reason [n_rec, batch],
+        moments [n_rec, dim_x+dim_u, 4], counts [n_rec, k_max+7], x_end, u_end)."""
+        n_ticks, stride = int(n_ticks), int(stride)
+        n_rec, nc, B = n_ticks // stride, self.dim_x + self.dim_u, self.batch
+        bufs = []
+
+        def dev(shape, dtype=None, init=None):
+            b = self.device_buffer(shape, dtype)
+            bufs.append(b)
+            return b.upload(init) if init is not None else b
+
+        def seq(a, per, width):
+            if a is None:
+                return None
+            shape = (n_ticks, B, width) if per else (n_ticks, width)
+            return dev(shape, init=np.asarray(a, dtype=self.np_dtype).reshape(shape))
+        try:
+            xd = dev((B, self.dim_x), init=self._host(x, (B, self.dim_x))[0])
+            ud = dev((B, self.dim_u), init=np.zeros((B, self.dim_u)) if u is None else self._host(u, (B, self.dim_u))[0])
+            t = np.zeros(n_rec)
+            rec = dict(stride=stride, x=dev((n_rec, B, self.dim_x)), u=dev((n_rec, B, self.dim_u)),
+                       n_ax=dev((n_rec, B), np.int32), reason=dev((n_rec, B), np.int32), t=t,
+                       centre=None if centre is None else dev((nc,), np.float64, np.asarray(centre, dtype=np.float64)),
+                       moments=dev((n_rec, nc, 4), np.float64), counts=dev((n_rec, self.k_max + 7), np.int32))
+            self.closed_loop_device(xd, ud, n_ticks, seq(ptau_seq, per_instance, self.dim_p * (self.dv + 1)) if self.dim_p else None,
+                                    per_instance, dist_seq_dev=seq(dist_seq, dist_per_instance, self.dim_x),
+                                    meas_seq_dev=seq(meas_seq, meas_per_instance, self.dim_x),
+                                    dist_per_instance=dist_per_instance, meas_per_instance=meas_per_instance, record=rec)
+            out = {k: rec[k].download() for k in ("x", "u", "n_ax", "reason", "moments", "counts")}  # (blocks on the stream)
+            out.update(t=t, x_end=xd.download(), u_end=ud.download())
+            return out
+        finally:
+            for b in bufs:
+                b.free()
 
     def synchronize(self):
         _check(load().cgmres_hip_synchronize(self._h))

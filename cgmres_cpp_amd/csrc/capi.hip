@@ -16,6 +16,7 @@
 #include "ctx_common.hip.h"
 #include "factory.hip.h"
 #include "gmres_plan.hip.h"
+#include "record_plan.hip.h"
 #include "util_kernels.hip.h"
 
 namespace {
@@ -31,6 +32,7 @@ struct Plugin {
   int (*probe)(const double*, const double*, const double*, const double*, double*, void*);
   const char* (*last_error)(void);
   cgm::HorizonFn* horizon;  // optional symbol: null in a plugin built before cgmres_hip_horizon_device existed
+  int32_t (*record)(void);  // optional symbol: null in a plugin whose contexts predate the record kernels (status_dev)
 };
 std::deque<Plugin>& plugins() {  // deque: find_plugin hands out pointers that must survive later push_backs
   static std::deque<Plugin> v;
@@ -180,6 +182,65 @@ int closed_loop(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const cg
   return h->closed_loop(x, u, n_ticks, sq);
 }
 
+// The input sequences of cgmres_hip_closed_loop_device_ex / ..._rec, checked: what both end in before closed_loop()
+int loop_seqs(cgmres_hip_handle h, const void* x, const void* u, int32_t n_ticks, const cgmres_hip_loop_inputs* in, cgm::LoopSeqs* out) {
+  if (n_ticks < 0) return fail(CGMRES_HIP_EINVAL, "n_ticks < 0");
+  cgm::LoopSeqs sq;
+  if (in) {
+    if (in->struct_size != int32_t(sizeof(cgmres_hip_loop_inputs)))
+      return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: struct_size %d, this library's cgmres_hip_loop_inputs has %d",
+                  in->struct_size, int(sizeof(cgmres_hip_loop_inputs)));
+    const int32_t pi[3] = {in->ptau_per_instance, in->dist_per_instance, in->meas_per_instance};
+    for (int32_t v : pi)
+      if (v != 0 && v != 1) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: a *_per_instance field is %d, not 0 or 1", v);
+    // the reference's alias guard (cgmres.hpp:119-124): an input sequence must not share bytes with the loop's outputs
+    const size_t es = h->cfg.dtype == CGMRES_HIP_F32 ? 4 : 8, B = size_t(h->cfg.batch);
+    auto overlaps = [&](const void* seq, int per_instance, const void* out, size_t out_bytes) {
+      if (!seq || !out) return false;
+      const uintptr_t a = reinterpret_cast<uintptr_t>(seq), b = reinterpret_cast<uintptr_t>(out);
+      const size_t seq_bytes = size_t(n_ticks) * (per_instance ? B : 1) * h->nx * es;
+      return a < b + out_bytes && b < a + seq_bytes;
+    };
+    const struct { const char* name; const void* p; int pi; } seqs[2] = {{"dist_seq_dev", in->dist_seq_dev, in->dist_per_instance},
+                                                                        {"meas_seq_dev", in->meas_seq_dev, in->meas_per_instance}};
+    for (const auto& s : seqs) {
+      if (overlaps(s.p, s.pi, x, B * h->nx * es))
+        return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: %s overlaps x_dev (cgmres.hpp DEBUG_MODE alias guard)", s.name);
+      if (overlaps(s.p, s.pi, u, B * h->nu * es))
+        return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: %s overlaps u_dev (cgmres.hpp DEBUG_MODE alias guard)", s.name);
+    }
+    sq.ptau = h->np ? in->ptau_seq_dev : nullptr, sq.ptau_per_instance = in->ptau_per_instance;
+    sq.dist = in->dist_seq_dev, sq.dist_per_instance = in->dist_per_instance;
+    sq.meas = in->meas_seq_dev, sq.meas_per_instance = in->meas_per_instance;
+  }
+  *out = sq;
+  return 0;
+}
+
+// Record j of a recorded loop (LoopSeqs::rec_take): the rows of the caller's logs, on the context's stream
+int take_loop_record(void* rec, cgmres_hip_ctx* c, int j, const void* x, const void* u, const int32_t* n_ax, const int32_t* reason,
+                     double t) {
+  const cgmres_hip_loop_record* r = static_cast<const cgmres_hip_loop_record*>(rec);
+  const size_t es = c->cfg.dtype == CGMRES_HIP_F32 ? 4 : 8, B = size_t(c->cfg.batch), row = size_t(j);
+  if (r->t_host) r->t_host[j] = t;
+  auto at = [&](auto* p, size_t bytes) {  // row j of a log, or null
+    return p ? static_cast<decltype(p)>(static_cast<void*>(static_cast<char*>(static_cast<void*>(p)) + row * bytes)) : nullptr;
+  };
+  return cgm::record_take(c, x, u, n_ax, reason,
+                          cgm::RecordOut{at(r->x_log_dev, B * c->nx * es), at(r->u_log_dev, B * c->nu * es), at(r->n_ax_log_dev, B * 4),
+                                         at(r->reason_log_dev, B * 4), r->centre_dev, at(r->moments_log_dev, size_t(c->nx + c->nu) * 32),
+                                         at(r->counts_log_dev, size_t(c->cfg.k_max + 7) * 4)});
+}
+
+// The record kernels touch members of cgmres_hip_ctx that a context built before them does not have: such a plugin is told
+// to rebuild, as for cgmres_hip_horizon_device.
+int plugin_records(cgmres_hip_handle h, const char* who) {
+  const Plugin* pl = find_plugin(h->cfg.model_id);
+  if (pl && !pl->record)
+    return fail(CGMRES_HIP_EINVAL, "%s: the plugin %s was built before this entry point existed: rebuild it", who, pl->path.c_str());
+  return 0;
+}
+
 __global__ void sincos_selftest_kernel(const double* a, double* s, double* c, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) cgm::sincos_f64(a[i], &s[i], &c[i]);
@@ -290,7 +351,7 @@ int cgmres_hip_register_model(const char* plugin_path, int32_t* model_id) {
   const int rc = open_plugin(
       plugins(), "model", "cgmres_hip_plugin_", plugin_path, model_id ? &n : nullptr, pl,
       {{"info", &info, true}, {"make", &pl.make, true}, {"probe", &pl.probe, true}, {"last_error", &pl.last_error, true},
-       {"horizon", &pl.horizon, false}},
+       {"horizon", &pl.horizon, false}, {"record", &pl.record, false}},
       [&](Plugin& q) {
         int32_t dims[5];
         double tun[6];
@@ -456,35 +517,78 @@ int cgmres_hip_closed_loop_device_ptau(cgmres_hip_handle h, void* x, void* u, in
 }
 int cgmres_hip_closed_loop_device_ex(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const cgmres_hip_loop_inputs* in) {
   NEED(h);
-  if (n_ticks < 0) return fail(CGMRES_HIP_EINVAL, "n_ticks < 0");
   cgm::LoopSeqs sq;
-  if (in) {
-    if (in->struct_size != int32_t(sizeof(cgmres_hip_loop_inputs)))
-      return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: struct_size %d, this library's cgmres_hip_loop_inputs has %d",
-                  in->struct_size, int(sizeof(cgmres_hip_loop_inputs)));
-    const int32_t pi[3] = {in->ptau_per_instance, in->dist_per_instance, in->meas_per_instance};
-    for (int32_t v : pi)
-      if (v != 0 && v != 1) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: a *_per_instance field is %d, not 0 or 1", v);
-    // the reference's alias guard (cgmres.hpp:119-124): an input sequence must not share bytes with the loop's outputs
-    const size_t es = h->cfg.dtype == CGMRES_HIP_F32 ? 4 : 8, B = size_t(h->cfg.batch);
-    auto overlaps = [&](const void* seq, int per_instance, const void* out, size_t out_bytes) {
-      if (!seq || !out) return false;
-      const uintptr_t a = reinterpret_cast<uintptr_t>(seq), b = reinterpret_cast<uintptr_t>(out);
-      const size_t seq_bytes = size_t(n_ticks) * (per_instance ? B : 1) * h->nx * es;
-      return a < b + out_bytes && b < a + seq_bytes;
-    };
-    const struct { const char* name; const void* p; int pi; } seqs[2] = {{"dist_seq_dev", in->dist_seq_dev, in->dist_per_instance},
-                                                                        {"meas_seq_dev", in->meas_seq_dev, in->meas_per_instance}};
-    for (const auto& s : seqs) {
-      if (overlaps(s.p, s.pi, x, B * h->nx * es))
-        return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: %s overlaps x_dev (cgmres.hpp DEBUG_MODE alias guard)", s.name);
-      if (overlaps(s.p, s.pi, u, B * h->nu * es))
-        return fail(CGMRES_HIP_EINVAL, "closed_loop_device_ex: %s overlaps u_dev (cgmres.hpp DEBUG_MODE alias guard)", s.name);
-    }
-    sq.ptau = h->np ? in->ptau_seq_dev : nullptr, sq.ptau_per_instance = in->ptau_per_instance;
-    sq.dist = in->dist_seq_dev, sq.dist_per_instance = in->dist_per_instance;
-    sq.meas = in->meas_seq_dev, sq.meas_per_instance = in->meas_per_instance;
+  if (int rc = loop_seqs(h, x, u, n_ticks, in, &sq)) return rc;
+  return closed_loop(h, x, u, n_ticks, sq);
+}
+int cgmres_hip_record_plan(int32_t n_ticks, int32_t stride, int32_t* n_rec, int32_t* launch_ticks, int32_t cap, int32_t* n_launches) {
+  if (n_ticks < 0) return fail(CGMRES_HIP_EINVAL, "record_plan: n_ticks < 0");
+  if (stride < 1) return fail(CGMRES_HIP_EINVAL, "record_plan: stride %d < 1", stride);
+  if (!cgm::record_plan(n_ticks, stride, CGMRES_HIP_TICKS_PER_LAUNCH, n_rec, launch_ticks, cap, n_launches))
+    return fail(CGMRES_HIP_EINVAL, "record_plan: %d ticks at stride %d take more than cap = %d launches", n_ticks, stride, cap);
+  return 0;
+}
+int cgmres_hip_ensemble_device(cgmres_hip_handle h, const void* x, const void* u, const cgmres_hip_ensemble_out* out) {
+  NEED(h);
+  if (!x) return fail(CGMRES_HIP_EINVAL, "ensemble_device: null x_dev");
+  if (!u) return fail(CGMRES_HIP_EINVAL, "ensemble_device: null u_dev");
+  if (!out) return fail(CGMRES_HIP_EINVAL, "ensemble_device: null out");
+  if (out->struct_size != int32_t(sizeof(cgmres_hip_ensemble_out)))
+    return fail(CGMRES_HIP_EINVAL, "ensemble_device: struct_size %d, this library's cgmres_hip_ensemble_out has %d", out->struct_size,
+                int(sizeof(cgmres_hip_ensemble_out)));
+  if (out->reserved != 0) return fail(CGMRES_HIP_EINVAL, "ensemble_device: cgmres_hip_ensemble_out.reserved must be 0 (got %d)", out->reserved);
+  if (!out->moments_dev && !out->counts_dev)
+    return fail(CGMRES_HIP_EINVAL, "ensemble_device: no output wanted (moments_dev and counts_dev are both null)");
+  if (int rc = plugin_records(h, "ensemble_device")) return rc;
+  ENTER(h);
+  const int32_t *n_ax = nullptr, *reason = nullptr;
+  if (int rc = h->status_dev(&n_ax, &reason)) return rc;
+  return cgm::record_take(h, x, u, n_ax, reason, cgm::RecordOut{nullptr, nullptr, nullptr, nullptr, out->centre_dev, out->moments_dev, out->counts_dev});
+}
+int cgmres_hip_closed_loop_device_rec(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const cgmres_hip_loop_inputs* in,
+                                      const cgmres_hip_loop_record* rec) {
+  NEED(h);
+  cgm::LoopSeqs sq;
+  if (int rc = loop_seqs(h, x, u, n_ticks, in, &sq)) return rc;
+  if (!rec) return closed_loop(h, x, u, n_ticks, sq);
+  if (rec->struct_size != int32_t(sizeof(cgmres_hip_loop_record)))
+    return fail(CGMRES_HIP_EINVAL, "closed_loop_device_rec: struct_size %d, this library's cgmres_hip_loop_record has %d",
+                rec->struct_size, int(sizeof(cgmres_hip_loop_record)));
+  if (rec->reserved[0] != 0 || rec->reserved[1] != 0)
+    return fail(CGMRES_HIP_EINVAL, "closed_loop_device_rec: cgmres_hip_loop_record.reserved must be 0 (got %d, %d)", rec->reserved[0],
+                rec->reserved[1]);
+  if (rec->stride < 1) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_rec: stride %d < 1", rec->stride);
+  if (!x) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_rec: null x_dev");
+  if (!u) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_rec: null u_dev");
+  if (!rec->x_log_dev && !rec->u_log_dev && !rec->n_ax_log_dev && !rec->reason_log_dev && !rec->t_host && !rec->moments_log_dev &&
+      !rec->counts_log_dev)
+    return closed_loop(h, x, u, n_ticks, sq);
+  // the alias guard of ..._ex, extended: a log shares no byte with x_dev, u_dev, another log or an input sequence
+  const size_t es = h->cfg.dtype == CGMRES_HIP_F32 ? 4 : 8, B = size_t(h->cfg.batch), n_rec = size_t(n_ticks / rec->stride);
+  const size_t nc = size_t(h->nx + h->nu), seq_rows = size_t(n_ticks);
+  struct Range { const char* name; const void* p; size_t bytes; };
+  const Range logs[6] = {{"x_log_dev", rec->x_log_dev, n_rec * B * h->nx * es},       {"u_log_dev", rec->u_log_dev, n_rec * B * h->nu * es},
+                         {"n_ax_log_dev", rec->n_ax_log_dev, n_rec * B * 4},          {"reason_log_dev", rec->reason_log_dev, n_rec * B * 4},
+                         {"moments_log_dev", rec->moments_log_dev, n_rec * nc * 32}, {"counts_log_dev", rec->counts_log_dev, n_rec * size_t(h->cfg.k_max + 7) * 4}};
+  const Range others[6] = {{"x_dev", x, B * h->nx * es},
+                           {"u_dev", u, B * h->nu * es},
+                           {"ptau_seq_dev", sq.ptau, seq_rows * (sq.ptau_per_instance ? B : 1) * h->np * (h->cfg.dv + 1) * es},
+                           {"dist_seq_dev", sq.dist, seq_rows * (sq.dist_per_instance ? B : 1) * h->nx * es},
+                           {"meas_seq_dev", sq.meas, seq_rows * (sq.meas_per_instance ? B : 1) * h->nx * es},
+                           {"centre_dev", rec->centre_dev, nc * 8}};
+  auto overlap = [](const Range& a, const Range& b) {
+    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a.p), pb = reinterpret_cast<uintptr_t>(b.p);
+    return pa < pb + b.bytes && pb < pa + a.bytes;
+  };
+  for (int i = 0; i < 6; ++i) {
+    for (const Range& o : others)
+      if (overlap(logs[i], o)) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_rec: %s overlaps %s (cgmres.hpp DEBUG_MODE alias guard)", logs[i].name, o.name);
+    for (int k = i + 1; k < 6; ++k)
+      if (overlap(logs[i], logs[k])) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_rec: %s overlaps %s (cgmres.hpp DEBUG_MODE alias guard)", logs[i].name, logs[k].name);
   }
+  if (int rc = plugin_records(h, "closed_loop_device_rec")) return rc;
+  sq.rec_stride = rec->stride, sq.rec_take = take_loop_record, sq.rec = const_cast<cgmres_hip_loop_record*>(rec);
   return closed_loop(h, x, u, n_ticks, sq);
 }
 int cgmres_hip_horizon_device(cgmres_hip_handle h, const void* x, const cgmres_hip_horizon_out* out) {

@@ -37,6 +37,7 @@ inline int fail(int code, const char* fmt, ...) {
 
 }  // namespace cgm
 
+struct cgmres_hip_ctx;
 namespace cgm {
 // Per-tick input sequences of the closed loop (cgmres_hip_loop_inputs, validated by capi.hip): device pointers,
 // [n_ticks][batch or 1][...]; null = absent
@@ -47,6 +48,14 @@ struct LoopSeqs {
   int dist_per_instance = 0;
   const void* meas = nullptr;  // v: added to the state the controller is shown
   int meas_per_instance = 0;
+  // The record of cgmres_hip_closed_loop_device_rec (record.hip.h): null rec_take = none.  A context cuts its launches by
+  // RecordCut(n_ticks, rec_stride, its ticks per launch) and, behind the launch that ends stride window j, calls
+  //   rec_take(rec, this, j, x, u, its n_ax, its reason, the handle's time when the window's last control() ran)
+  // A pointer, not a name: the function lives in the library, the context of a user model in its plugin.
+  int rec_stride = 0;
+  int (*rec_take)(void* rec, cgmres_hip_ctx* c, int j, const void* x, const void* u, const int32_t* n_ax,
+                  const int32_t* reason, double t) = nullptr;
+  void* rec = nullptr;
 };
 }  // namespace cgm
 
@@ -58,6 +67,9 @@ struct cgmres_hip_ctx {
   bool own_stream = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<void*> owned;
+  // workgroup partials of the record kernels (record.hip.h), grown on demand by the library, never by a context
+  double* rec_scratch = nullptr;
+  size_t rec_scratch_n = 0;
 
   virtual ~cgmres_hip_ctx() {
     (void)hipSetDevice(cfg.device);
@@ -128,4 +140,6 @@ struct cgmres_hip_ctx {
   virtual int hook_prepare(void*, const void*) = 0;
   virtual int hook_Ax(void*, const void*) = 0;
   virtual int hook_gmres(void*, const void*) = 0;
+  // device addresses of what get_status copies: [batch] each, caller order, in every mapping
+  virtual int status_dev(const int32_t** n_ax, const int32_t** reason) = 0;
 };

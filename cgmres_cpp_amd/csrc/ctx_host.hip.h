@@ -15,6 +15,7 @@
 #pragma once
 #include "ctx_common.hip.h"
 #include "horizon.hip.h"
+#include "record_plan.hip.h"
 #include "util_kernels.hip.h"
 
 namespace cgm {
@@ -111,6 +112,15 @@ struct CtxHost : cgmres_hip_ctx {
     if (reason) HIP_TRY(hipMemcpyAsync(reason, self().P.reason, size_t(cfg.batch) * 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
+  }
+  int status_dev(const int32_t** n_ax, const int32_t** reason) override {
+    *n_ax = self().P.n_ax, *reason = self().P.reason;
+    return 0;
+  }
+  // Record j of a recorded closed loop, on the stream behind the launch that ended its stride window.  x, u, n_ax and
+  // reason are in caller order and instance-major in every mapping, so the record has no per-mapping code.
+  int record(const LoopSeqs& sq, int j, const void* x, const void* u, T t_tick) {
+    return sq.rec_take(sq.rec, this, j, x, u, self().P.n_ax, self().P.reason, double(t_tick));
   }
 };
 

@@ -95,7 +95,12 @@ struct CtxLane final : CtxHost<M, T, CtxLane<M, T>> {
     const size_t d_tick = size_t(sq.dist_per_instance ? cfg.batch : 1) * nx, m_tick = size_t(sq.meas_per_instance ? cfg.batch : 1) * nx;
     P.dist_inst = sq.dist_per_instance ? nx : 0, P.meas_inst = sq.meas_per_instance ? nx : 0;
     int rc = 0;
-    for (int i = 0; i < n_ticks && !rc; ++i) {
+    RecordCut cut(n_ticks, sq.rec_take ? sq.rec_stride : 0, 1);  // (one tick per launch: the cut only says where a record is due)
+    while (!cut.done() && !rc) {
+      const int i = cut.i;
+      bool rec = false;
+      cut.next(&rec);
+      const T t_tick = t;
       if (sq.ptau && all) {  // set_ptau before this tick (cgmres.hpp:36-39), device to device
         dim3 grid((cfg.batch + 255) / 256, all);
         to_element_major<T><<<grid, 256, 0, stream>>>(P.ptau, static_cast<const T*>(sq.ptau) + i * per_tick, cfg.batch,
@@ -105,6 +110,7 @@ struct CtxLane final : CtxHost<M, T, CtxLane<M, T>> {
       P.dist = dseq ? dseq + size_t(i) * d_tick : nullptr;
       P.meas = mseq ? mseq + size_t(i) * m_tick : nullptr;
       rc = launch_tick(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x));
+      if (!rc && rec) rc = Host::record(sq, cut.i / sq.rec_stride - 1, x, u, t_tick);
     }
     P.dist = nullptr, P.meas = nullptr;  // control() and the hooks take neither
     return rc;

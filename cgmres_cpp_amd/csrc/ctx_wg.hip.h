@@ -224,8 +224,12 @@ struct CtxWg final : CtxHost<M, T, CtxWg<M, T>> {
     // (a lambda, so that a failed launch check leaves through the line below it, which takes the per-launch pointers off
     // the handle: a later control() must not meet a stale sequence or PlantSeqs record)
     auto launches = [&]() -> int {
-      for (int i = 0; i < n_ticks; i += CGM_FUSE_MAX) {
-        const int n = n_ticks - i < CGM_FUSE_MAX ? n_ticks - i : CGM_FUSE_MAX;
+      // the launch sizes: today's cut, or with a record the cut of record_plan.hip.h (every recorded tick ends a launch)
+      RecordCut cut(n_ticks, sq.rec_take ? sq.rec_stride : 0, CGM_FUSE_MAX);
+      while (!cut.done()) {
+        const int i = cut.i;
+        bool rec = false;
+        const int n = cut.next(&rec);
         P.ptau_seq = seq ? seq + size_t(i) * per_tick : nullptr;  // the kernel reloads ptau at the top of every tick
         if (plant_in) {  // this launch's rows, through the device-resident record the kernel reads (stream-ordered)
           PlantSeqs<T> q = ps;
@@ -240,10 +244,14 @@ struct CtxWg final : CtxHost<M, T, CtxWg<M, T>> {
           HIP_TRY(hipGetLastError());
           P.perm = perm_dev;
         }
+        T t_last = t;  // the time of the launch's last control(), by the statements of launch_ticks
+        for (int k = 1; k < n; ++k) t_last = t_last + P.dt;
         const int rc = launch_ticks(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x), n);
         P.perm = nullptr;
         have_counts = true;
         if (rc) return rc;
+        if (rec)
+          if (int rr = Host::record(sq, cut.i / sq.rec_stride - 1, x, u, t_last)) return rr;
       }
       return 0;
     };

@@ -16,6 +16,17 @@ cgmres_hip_ctx* make_semiactive_f64(const cgmres_hip_config& cfg, int* resolved)
 cgmres_hip_ctx* make_semiactive_f32(const cgmres_hip_config& cfg, int* resolved);
 HorizonFn horizon_pendulum_f64, horizon_pendulum_f32, horizon_msd_f64, horizon_msd_f32, horizon_semiactive_f64,
     horizon_semiactive_f32;
+// One record of a closed loop / the ensemble of a batch (record.hip.h), on the context's stream: the log rows and the
+// statistics of x [batch][nx], u [batch][nu] and the status arrays given; any destination may be null.  Independent of
+// model and mapping, so there is one function, in inst_record.hip.
+struct RecordOut {
+  void *x_log, *u_log;
+  int32_t *n_ax_log, *reason_log;
+  const double* centre;
+  double* moments;
+  int32_t* counts;
+};
+int record_take(cgmres_hip_ctx* c, const void* x, const void* u, const int32_t* n_ax, const int32_t* reason, const RecordOut& o);
 #ifdef CGM_STAMPS
 long long* debug_stamps_ptr();  // diagnostic build only: stamp buffer of the last pendulum/f64 wg context
 #endif

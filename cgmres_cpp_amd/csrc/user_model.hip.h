@@ -212,7 +212,17 @@ extern "C" int cgmres_hip_plugin_debug_lds_oob(void) {
   }
 #endif
 
-// The entry points of a model plugin (bound by cgmres_hip_register_model in capi.hip): four required, horizon optional.
+// The second optional entry point says that the plugin's contexts have cgmres_hip_ctx::status_dev and the record members
+// (cgmres_hip_closed_loop_device_rec, cgmres_hip_ensemble_device); the library refuses those two calls, and nothing else,
+// for a plugin without it, which the tests imitate with -DCGM_PLUGIN_WITHOUT_RECORD.
+#ifdef CGM_PLUGIN_WITHOUT_RECORD
+#define CGM_PLUGIN_RECORD
+#else
+#define CGM_PLUGIN_RECORD \
+  int32_t cgmres_hip_plugin_record(void) { return 1; }
+#endif
+
+// The entry points of a model plugin (bound by cgmres_hip_register_model in capi.hip): four required, horizon and record optional.
 #define CGMRES_HIP_DEFINE_PLUGIN(MODEL)                                                                          \
   extern "C" {                                                                                                   \
   int32_t cgmres_hip_plugin_abi(void) { return CGMRES_HIP_ABI_VERSION; }                                         \
@@ -247,4 +257,5 @@ extern "C" int cgmres_hip_plugin_debug_lds_oob(void) {
   }                                                                                                              \
   const char* cgmres_hip_plugin_last_error(void) { return cgm::g_err.c_str(); }                                  \
   CGM_PLUGIN_HORIZON(MODEL)                                                                                      \
+  CGM_PLUGIN_RECORD                                                                                              \
   }

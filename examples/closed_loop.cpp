@@ -4,6 +4,9 @@
 //   closed_loop msd        [ticks] [out_prefix]   two-mass spring damper      (dv=50, k_max=5)
 //   closed_loop semiactive [ticks] [out_prefix]   semi-active damper          (dv=50, k_max=5)
 //   closed_loop multiple   [ticks] [out_prefix]   msd + pendulum stepped in one loop (two controllers)
+//   ... --device-loop                              (the four above, anywhere on the line) the loop runs in ONE call of
+//                                                  the device-resident closed loop with a stride-1 record, and the two
+//                                                  files are written from its logs: same lines, no host call per tick
 //   closed_loop batch <B>  [ticks]                B perturbed pendulum controllers, dv=50, k_max=10, CgmresBatch
 //   closed_loop sharded <B> <dev,dev,...> [ticks]  the same batch owned shard by shard on the listed devices
 //                                                  (CgmresBatchSharded; a device may be listed twice), checked against
@@ -77,8 +80,13 @@ static const double kPendX0[4] = {kPi, kPi, 0.0, 0.0}, kPendU0[3] = {0.0, 3.0, 0
 static const double kMsdX0[4] = {2.0, 2.0, 0.0, 0.0}, kMsdU0[6] = {0.0, 0.0, 10.0, 10.0, 5e-4, 5e-4}, kMsdP[2] = {1, -1};
 static const double kSemiX0[2] = {2.0, 0.0}, kSemiU0[3] = {0.028393761456740, 0.166095020295846, 0.030103250483332};
 
+static bool g_device_loop = false;  // --device-loop
+template <class Model>
+static int run_single_device(const char* prefix, int ticks, const double* x0, const double* u0, const double* p);
+
 template <class Model, class Plant>
 static int run_single(const char* prefix, int ticks, const double* x0, const double* u0, const double* p) {
+  if (g_device_loop) return run_single_device<Model>(prefix, ticks, x0, u0, p);
   Loop<Model, Plant> loop(prefix, x0, u0, p);
   double t_all = 0;
   for (int i = 0; i < ticks; ++i) {
@@ -91,7 +99,89 @@ static int run_single(const char* prefix, int ticks, const double* x0, const dou
   return 0;
 }
 
+// --device-loop: the same controller as a batch of one whose loop never leaves the GPU.  One call records every tick
+// (cgmres_hip_closed_loop_device_rec, stride 1): x after the plant step, the u that produced it and the time of the
+// tick's control() — the three things a line of the files holds.  The plant is the model's own dxdt, as in the mains.
+template <class Model>
+struct DeviceLoop {
+  CgmresBatch<Model> controller{1};
+  std::vector<double> x, u, t;
+  double *x_dev = nullptr, *u_dev = nullptr, *x_log = nullptr, *u_log = nullptr;
+  std::string prefix;
+  int ticks;
+  DeviceLoop(const std::string& prefix_, int ticks_, const double* x0, const double* u0, const double* p)
+      : x(x0, x0 + Model::dim_x), u(u0, u0 + Model::dim_u), t(ticks_ > 0 ? ticks_ : 1), prefix(prefix_), ticks(ticks_) {
+    std::vector<double> pt(Model::dim_p * (Model::dv + 1) + 1, 0.0);
+    for (int s = 0; s <= Model::dv; ++s)
+      for (int j = 0; j < Model::dim_p; ++j) pt[Model::dim_p * s + j] = p[j];
+    controller.set_ptau(pt.data());
+    controller.init_u0(u.data());
+    controller.init_u0_newton(u.data(), x.data(), pt.data(), 10);
+    const cgmres_hip_handle h = controller.native_handle();
+    const size_t n = size_t(ticks > 0 ? ticks : 1);
+    double** bufs[4] = {&x_dev, &u_dev, &x_log, &u_log};
+    const size_t bytes[4] = {sizeof(double) * Model::dim_x, sizeof(double) * Model::dim_u, sizeof(double) * Model::dim_x * n,
+                             sizeof(double) * Model::dim_u * n};
+    for (int i = 0; i < 4; ++i) cgmres_detail::check(cgmres_hip_malloc(h, reinterpret_cast<void**>(bufs[i]), bytes[i]), "malloc");
+    cgmres_detail::check(cgmres_hip_memcpy_h2d(h, x_dev, x.data(), bytes[0]), "memcpy_h2d");
+    cgmres_detail::check(cgmres_hip_memcpy_h2d(h, u_dev, u.data(), bytes[1]), "memcpy_h2d");
+  }
+  ~DeviceLoop() {
+    for (double* q : {x_dev, u_dev, x_log, u_log}) cgmres_hip_free(controller.native_handle(), q);
+  }
+  void enqueue() {
+    cgmres_hip_loop_record rec = {};
+    rec.struct_size = int32_t(sizeof rec), rec.stride = 1;
+    rec.x_log_dev = x_log, rec.u_log_dev = u_log, rec.t_host = t.data();
+    controller.closed_loop_device(x_dev, u_dev, ticks, nullptr, rec);
+  }
+  void write_files() {
+    const cgmres_hip_handle h = controller.native_handle();
+    std::vector<double> xs(size_t(ticks) * Model::dim_x + 1), us(size_t(ticks) * Model::dim_u + 1);
+    cgmres_detail::check(cgmres_hip_memcpy_d2h(h, xs.data(), x_log, sizeof(double) * Model::dim_x * ticks), "memcpy_d2h");
+    cgmres_detail::check(cgmres_hip_memcpy_d2h(h, us.data(), u_log, sizeof(double) * Model::dim_u * ticks), "memcpy_d2h");
+    FILE *fx = fopen((prefix + "_x.txt").c_str(), "w"), *fu = fopen((prefix + "_u.txt").c_str(), "w");
+    if (!fx || !fu) {
+      perror("fopen");
+      exit(1);
+    }
+    for (int i = 0; i < ticks; ++i) {
+      fprintf(fx, "%f", t[i]);
+      fprintf(fu, "%f", t[i]);
+      for (int c = 0; c < Model::dim_x; ++c) fprintf(fx, "\t%f", xs[size_t(i) * Model::dim_x + c]);
+      for (int c = 0; c < Model::dim_u; ++c) fprintf(fu, "\t%f", us[size_t(i) * Model::dim_u + c]);
+      fprintf(fx, "\n");
+      fprintf(fu, "\n");
+    }
+    fclose(fx);
+    fclose(fu);
+  }
+};
+
+template <class Model>
+static int run_single_device(const char* prefix, int ticks, const double* x0, const double* u0, const double* p) {
+  DeviceLoop<Model> loop(prefix, ticks, x0, u0, p);
+  const double t0 = now_s();
+  loop.enqueue();
+  loop.controller.synchronize();
+  const double t_all = now_s() - t0;  // (control and plant together: they share the kernels)
+  loop.write_files();
+  printf("Elapsed time = %f\n", t_all);
+  return 0;
+}
+
 static int run_multiple(const char* prefix, int ticks) {  // multiple_controller/main.cpp:89-143
+  if (g_device_loop) {  // two independent controllers: their two loops are enqueued back to back and overlap
+    DeviceLoop<examples::MsdModel<50, 5>> l1(std::string(prefix) + "1", ticks, kMsdX0, kMsdU0, kMsdP);
+    DeviceLoop<examples::PendulumModel<25, 5>> l2(std::string(prefix) + "2", ticks, kPendX0, kPendU0, kPendP);
+    const double t0 = now_s();
+    l1.enqueue(), l2.enqueue();
+    l1.controller.synchronize(), l2.controller.synchronize();
+    const double t_all = now_s() - t0;
+    l1.write_files(), l2.write_files();
+    printf("Elapsed time = %f\n", t_all);
+    return 0;
+  }
   using M1 = examples::MsdModel<50, 5>;
   using M2 = examples::PendulumModel<25, 5>;
   Loop<M1, examples::MsdPlant> l1(std::string(prefix) + "1", kMsdX0, kMsdU0, kMsdP);
@@ -216,6 +306,12 @@ static int run_sharded(int B, const char* devlist, int ticks) {
 }
 
 int main(int argc, char** argv) {
+  for (int i = 1; i < argc; ++i)  // the switch may stand anywhere; the positional arguments close up
+    if (!strcmp(argv[i], "--device-loop")) {
+      g_device_loop = true;
+      for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+      --argc, --i;
+    }
   const char* which = argc > 1 ? argv[1] : "pendulum";
   if (!strcmp(which, "batch")) return run_batch(argc > 2 ? atoi(argv[2]) : 4096, argc > 3 ? atoi(argv[3]) : 100);
   if (!strcmp(which, "sharded"))
@@ -232,6 +328,6 @@ int main(int argc, char** argv) {
     return run_single<examples::SemiactiveModel<50, 5>, examples::SemiactivePlant>(
         prefix ? prefix : "semiactive_damper", ticks < 0 ? 20001 : ticks, kSemiX0, kSemiU0, kSemiX0 /*unused: dim_p = 0*/);
   if (!strcmp(which, "multiple")) return run_multiple(prefix ? prefix : "multiple_controller_", ticks < 0 ? 10001 : ticks);
-  fprintf(stderr, "usage: %s pendulum|msd|semiactive|multiple [ticks] [prefix]  |  batch <B> [ticks]  |  sharded <B> <dev,dev,..> [ticks]\n", argv[0]);
+  fprintf(stderr, "usage: %s pendulum|msd|semiactive|multiple [ticks] [prefix] [--device-loop]  |  batch <B> [ticks]  |  sharded <B> <dev,dev,..> [ticks]\n", argv[0]);
   return 2;
 }

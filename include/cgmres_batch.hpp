@@ -71,6 +71,19 @@ class CgmresBatch {
   void closed_loop_device(double* x_dev, double* u_dev, int32_t n_ticks, const cgmres_hip_loop_inputs& in) {
     cgmres_detail::check(cgmres_hip_closed_loop_device_ex(handle_, x_dev, u_dev, n_ticks, &in), "closed_loop_device_ex");
   }
+  // the same loop, every rec.stride-th tick RECORDED into the device logs `rec` names (x after the plant step, the u that
+  // produced it, the solver status, the ensemble statistics; t into host memory) — cgmres_hip_closed_loop_device_rec.
+  // `in` may be null (no input sequences); `rec.struct_size` must be sizeof(cgmres_hip_loop_record)
+  void closed_loop_device(double* x_dev, double* u_dev, int32_t n_ticks, const cgmres_hip_loop_inputs* in,
+                          const cgmres_hip_loop_record& rec) {
+    cgmres_detail::check(cgmres_hip_closed_loop_device_rec(handle_, x_dev, u_dev, n_ticks, in, &rec), "closed_loop_device_rec");
+  }
+  // mean / spread sums, min, max per component of x_dev, u_dev over the instances whose row is finite, and the counts of
+  // the controllers' current status, into the device arrays `out` names — cgmres_hip_ensemble_device.  Asynchronous on
+  // the handle's stream; changes no state
+  void ensemble_device(const double* x_dev, const double* u_dev, const cgmres_hip_ensemble_out& out) {
+    cgmres_detail::check(cgmres_hip_ensemble_device(handle_, x_dev, u_dev, &out), "ensemble_device");
+  }
   // what F_func builds (cgmres.hpp:113-162) with the controllers' current U, ptau and t at x_dev [batch][dim_x]: the
   // predicted state and costate trajectories, F and ||F|| into the device arrays `out` names (null = not wanted;
   // `out.struct_size` must be sizeof(cgmres_hip_horizon_out)).  Asynchronous on the handle's stream; changes no state
@@ -98,7 +111,9 @@ class CgmresBatch {
 // rule.  A tick needs no exchange between shards, so there is no collective here: set-up calls and host-pointer
 // control() fan out on one host thread per shard (each blocks on its own device), the device-resident closed loop is
 // enqueued on every shard's stream and runs concurrently.  `devices` may name a device more than once (two shards on
-// one card: how the tests run it).
+// one card: how the tests run it).  The record of a closed loop and the ensemble (CgmresBatch::closed_loop_device with a
+// cgmres_hip_loop_record, ensemble_device) are not offered here: an ensemble over shards needs a combine across devices;
+// shard(r) gives the per-shard calls.
 template <class Model>
 class CgmresBatchSharded {
  public:

@@ -246,6 +246,79 @@ typedef struct cgmres_hip_horizon_out {
   void* fnorm_dev;       /* [batch]               sqrt(sum_e F[e]^2), e ascending, accumulated in the handle's scalar type */
 } cgmres_hip_horizon_out;
 int cgmres_hip_horizon_device(cgmres_hip_handle h, const void* x_dev, const cgmres_hip_horizon_out* out);
+/* ---- the ensemble of a batch and the record of a closed loop: the lines <example>/main.cpp:75-82 writes ------------- */
+/* The statistics of ONE row of the batch: x_dev [batch][dim_x], u_dev [batch][dim_u] (the caller's, handle dtype) and the
+ * status arrays the handle currently holds (what cgmres_hip_get_status would return).  Instance b COUNTS when all
+ * dim_x + dim_u values of its row are finite.  Component c runs over x, then u; with z = double(value) - centre[c] over
+ * the counting instances
+ *     moments[c] = { s1 = sum z, s2 = sum z*z, min, max }    (min / max of the values themselves; no counting instance:
+ *                                                              s1 = s2 = 0, min = +inf, max = -inf)
+ * in double for fp32 handles too.  The caller forms mean = centre + s1/n and var = s2/n - (s1/n)^2: with the set point as
+ * centre nothing cancels, which is why there is a centre.
+ *     counts[0 .. k_max]             histogram of n_ax over ALL instances
+ *     counts[k_max+1 .. k_max+5]     instances per CGMRES_HIP_EXIT_* code 0 .. 4, over ALL instances
+ *     counts[k_max+6]                the counting instances (n above)
+ * The sums use no floating-point atomics and a fixed order: two runs from the same state give the same bits.  Stream-
+ * ordered on the handle's stream and asynchronous, changing nothing a later tick reads (the contract of
+ * cgmres_hip_horizon_device).  Every mapping, both dtypes, built-in and user models (the kernel is the library's, independent
+ * of the model: a plugin holds none of it).  CGMRES_HIP_EINVAL, each with its own text: x_dev or u_dev NULL, out NULL, a
+ * struct_size other than sizeof(cgmres_hip_ensemble_out), a non-zero reserved, both outputs NULL, counts for
+ * k_max + 7 > 8192; a user model whose plugin was built before this entry point existed (rebuild the plugin: everything
+ * else of it keeps working). */
+typedef struct cgmres_hip_ensemble_out {
+  int32_t struct_size;      /* sizeof(cgmres_hip_ensemble_out); anything else: CGMRES_HIP_EINVAL */
+  int32_t reserved;         /* 0; anything else: CGMRES_HIP_EINVAL */
+  const double* centre_dev; /* [dim_x+dim_u] doubles, or NULL = zeros */
+  double* moments_dev;      /* [dim_x+dim_u][4] = {s1, s2, min, max}, always double; NULL: not wanted */
+  int32_t* counts_dev;      /* [k_max+7]; NULL: not wanted */
+} cgmres_hip_ensemble_out;
+int cgmres_hip_ensemble_device(cgmres_hip_handle h, const void* x_dev, const void* u_dev, const cgmres_hip_ensemble_out* out);
+/* Instances one workgroup of the record kernel covers per grid step (a batch above it has several partials to combine:
+ * what a test of the ensemble wants to know). */
+#define CGMRES_HIP_RECORD_BLOCK 256
+/* cgmres_hip_closed_loop_device_ex that RECORDS every stride-th tick: tick k (0-based within the call) is recorded iff
+ * (k+1) % stride == 0, n_rec = n_ticks / stride records in all; ticks behind the last recorded one still run.  The phase
+ * restarts with every call: a caller who chains calls uses multiples of the stride.  Record j (tick k = (j+1)*stride - 1)
+ * is the reference's own output line (<example>/main.cpp:75-82), the state AFTER the plant step and the input that
+ * produced it:
+ *     x_log[j] = x_{k+1}   (under disturbance / noise inputs the TRUE state, disturbance included)
+ *     u_log[j] = u_k
+ *     n_ax_log[j], reason_log[j] = what cgmres_hip_get_status would return after tick k
+ *     t_host[j] = the handle's time when tick k's control() ran, i.e. before t += dt (cgmres.hpp:107): main.cpp's first
+ *                 column.  HOST memory, filled before the call returns.
+ *     moments_log[j], counts_log[j] = cgmres_hip_ensemble_device of that row, with centre_dev
+ * Every output pointer may be NULL.  rec == NULL, or all seven outputs NULL: exactly cgmres_hip_closed_loop_device_ex(h,
+ * x_dev, u_dev, n_ticks, in), launch for launch.  The record is taken BETWEEN kernel launches, by a kernel of its own on
+ * the same stream: the launches are cut so that every recorded tick is the last tick of one (cgmres_hip_record_plan), and
+ * the loop is, launch for launch and bit for bit, the loop of a caller who calls ..._ex once per stride window and
+ * downloads x, u and the status in between.  A stride that is a multiple of CGMRES_HIP_TICKS_PER_LAUNCH adds no launch
+ * but the records'; below that the caller trades fusion for resolution.  n_ticks == 0 does nothing.  CGMRES_HIP_EINVAL,
+ * each with its own text: everything ..._ex refuses; a struct_size other than sizeof(cgmres_hip_loop_record), a non-zero
+ * reserved, stride < 1, x_dev or u_dev NULL, a device log whose byte range overlaps x_dev, u_dev, another log of the same
+ * call or a sequence of `in`; a user model whose plugin was built before this entry point existed (rebuild the plugin).
+ * Asynchronous on the handle's stream. */
+typedef struct cgmres_hip_loop_record {
+  int32_t struct_size;      /* sizeof(cgmres_hip_loop_record); anything else: CGMRES_HIP_EINVAL */
+  int32_t stride;           /* >= 1 */
+  int32_t reserved[2];      /* 0 */
+  void* x_log_dev;          /* [n_rec][batch][dim_x], handle dtype */
+  void* u_log_dev;          /* [n_rec][batch][dim_u] */
+  int32_t* n_ax_log_dev;    /* [n_rec][batch] */
+  int32_t* reason_log_dev;  /* [n_rec][batch] */
+  double* t_host;           /* HOST memory [n_rec] */
+  const double* centre_dev; /* as in cgmres_hip_ensemble_out */
+  double* moments_log_dev;  /* [n_rec][dim_x+dim_u][4] */
+  int32_t* counts_log_dev;  /* [n_rec][k_max+7] */
+} cgmres_hip_loop_record;
+int cgmres_hip_closed_loop_device_rec(cgmres_hip_handle h, void* x_dev, void* u_dev, int32_t n_ticks,
+                                      const cgmres_hip_loop_inputs* in, const cgmres_hip_loop_record* rec);
+/* The launch cut of ..._rec on the mappings that fuse ticks: *n_rec = n_ticks / stride, *n_launches launches, their tick
+ * counts in launch_ticks[0 .. *n_launches) (cap = its capacity; launch_ticks NULL: only the two numbers are wanted).  Each
+ * stride window is cut exactly as a fresh call of `stride` ticks is cut (CGMRES_HIP_TICKS_PER_LAUNCH, ..., then the
+ * remainder), the tail behind the last record as a fresh call of the remaining ticks.  n_rec / n_launches may be NULL.
+ * CGMRES_HIP_EINVAL: n_ticks < 0, stride < 1, cap too small.  Pure host arithmetic: needs no GPU. */
+int cgmres_hip_record_plan(int32_t n_ticks, int32_t stride, int32_t* n_rec, int32_t* launch_ticks, int32_t cap,
+                           int32_t* n_launches);
 int cgmres_hip_synchronize(cgmres_hip_handle h);
 
 /* ---- state: the private members of Cgmres (cgmres.hpp:195-202) and Gmres (gmres.hpp:120-124) ------ */
