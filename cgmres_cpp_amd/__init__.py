@@ -40,7 +40,10 @@ SYMBOLS = [
     "cgmres_hip_timer_start", "cgmres_hip_timer_stop", "cgmres_hip_malloc", "cgmres_hip_free",
     "cgmres_hip_memcpy_h2d", "cgmres_hip_memcpy_d2h", "cgmres_hip_state_rows", "cgmres_hip_horizon_device",
     "cgmres_hip_ensemble_device", "cgmres_hip_closed_loop_device_rec", "cgmres_hip_record_plan",
+    "cgmres_hip_plant_info", "cgmres_hip_plant_step_device", "cgmres_hip_closed_loop_device_plant",
 ]
+PLANT_EULER, PLANT_RK4 = 0, 1  # CGMRES_HIP_PLANT_*
+PLANT_INTEGRATORS = {"euler": PLANT_EULER, "rk4": PLANT_RK4}
 
 
 class Config(C.Structure):
@@ -76,6 +79,22 @@ class LoopRecord(C.Structure):
                 ("u_log_dev", C.c_void_p), ("n_ax_log_dev", C.c_void_p), ("reason_log_dev", C.c_void_p),
                 ("t_host", C.c_void_p), ("centre_dev", C.c_void_p), ("moments_log_dev", C.c_void_p),
                 ("counts_log_dev", C.c_void_p)]
+
+
+class LoopPlant(C.Structure):
+    """struct cgmres_hip_loop_plant (include/cgmres_hip.h): the plant of cgmres_hip_closed_loop_device_plant."""
+    _fields_ = [("struct_size", C.c_int32), ("integrator", C.c_int32), ("substeps", C.c_int32),
+                ("theta_per_instance", C.c_int32), ("theta_dev", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
+class Plant:
+    """The plant of a closed loop that is not the controller's model stepped by one Euler step: `substeps` steps of
+    dt/substeps of integrator "euler" | "rk4" on the model's state equation, with the plant parameters theta
+    (plant_info(model): a device buffer [batch, n_theta] or one row [n_theta]; None = nominal).  theta_per_instance: for a
+    raw address, whose shape cannot be seen; otherwise decided by the buffer's shape."""
+
+    def __init__(self, integrator="rk4", substeps=4, theta=None, theta_per_instance=None):
+        self.integrator, self.substeps, self.theta, self.theta_per_instance = integrator, int(substeps), theta, theta_per_instance
 
 
 class CgmresHipError(RuntimeError):
@@ -148,6 +167,11 @@ def load():
         lib.cgmres_hip_ensemble_device.argtypes = [vp, vp, vp, C.POINTER(EnsembleOut)]
         lib.cgmres_hip_closed_loop_device_rec.argtypes = [vp, vp, vp, i32, C.POINTER(LoopInputs), C.POINTER(LoopRecord)]
         lib.cgmres_hip_record_plan.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(i32)]
+    if hasattr(lib, "cgmres_hip_closed_loop_device_plant"):  # (absent from A/B builds of older sources, tools/ab_build.py)
+        lib.cgmres_hip_plant_info.argtypes = [i32, C.POINTER(i32), C.POINTER(C.c_double), i32]
+        lib.cgmres_hip_plant_step_device.argtypes = [vp, vp, vp, C.POINTER(LoopPlant)]
+        lib.cgmres_hip_closed_loop_device_plant.argtypes = [vp, vp, vp, i32, C.POINTER(LoopInputs), C.POINTER(LoopRecord),
+                                                            C.POINTER(LoopPlant)]
     if hasattr(lib, "cgmres_hip_state_rows"):  # (absent from A/B builds of older sources, tools/ab_build.py)
         lib.cgmres_hip_state_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
     _lib = lib
@@ -181,6 +205,17 @@ def model_info(model):
     _check(load().cgmres_hip_model_info(model, d, t))
     return dict(zip(("dim_x", "dim_u", "dim_p", "dv", "k_max"), list(d)),
                 **dict(zip(("dt", "h", "zeta", "Tf", "alpha", "tol"), list(t))))
+
+
+def plant_info(model):
+    """cgmres_hip_plant_info: dict(n_theta, nominal [n_theta]) — the plant parameters of a model, in the order of theta
+    (pendulum: As, Bs, A52, C22, A32a, A32, A32b; msd: m1, m2, d1, d2, k1, k2; semiactive: a, b; a user model: none).  No GPU."""
+    model = MODEL_IDS.get(model, model)
+    n = C.c_int32()
+    _check(load().cgmres_hip_plant_info(model, C.byref(n), None, 0))
+    nom = (C.c_double * max(1, n.value))()
+    _check(load().cgmres_hip_plant_info(model, C.byref(n), nom, n.value))
+    return dict(n_theta=n.value, nominal=np.array(nom[:n.value], dtype=np.float64))
 
 
 def model_probe(model, x, u, p, lmd, device=0):
@@ -438,18 +473,28 @@ class CgmresBatch:
         return li
 
     def closed_loop_device(self, x_dev, u_dev, n_ticks, ptau_seq_dev=None, per_instance=True, *, dist_seq_dev=None,
-                           meas_seq_dev=None, dist_per_instance=True, meas_per_instance=True, record=None):
+                           meas_seq_dev=None, dist_per_instance=True, meas_per_instance=True, record=None, plant=None):
         """n_ticks of the example main loop on the device.  ptau_seq_dev: optional device array of per-tick parameter
         horizons, [n_ticks, batch, dim_p*(dv+1)] (per_instance) or [n_ticks, dim_p*(dv+1)] — `set_ptau` before every tick.
         dist_seq_dev / meas_seq_dev: optional device arrays [n_ticks, batch, dim_x] (or [n_ticks, dim_x], broadcast) of a
         process disturbance d and a measurement noise v: y_k = x_k + v_k, u_k = control(y_k),
         x_{k+1} = (x_k + f(x_k, u_k)*dt) + d_k; x_dev holds the TRUE state (cgmres_hip_closed_loop_device_ex).
         record: a dict(stride=1, x=, u=, n_ax=, reason=, t=, centre=, moments=, counts=) of device buffers (t: a host float64
-        array), every one optional — every stride-th tick is recorded into them (cgmres_hip_closed_loop_device_rec)."""
+        array), every one optional — every stride-th tick is recorded into them (cgmres_hip_closed_loop_device_rec).
+        plant: a Plant — x_{k+1} = Phi(x_k, u_k) + d_k with its integrator, substeps and parameters instead of the model's
+        Euler step, one tick per launch (cgmres_hip_closed_loop_device_plant)."""
         xp = _ptr(x_dev, self.np_dtype, self.batch * self.dim_x)
         up = _ptr(u_dev, self.np_dtype, self.batch * self.dim_u)
         if ptau_seq_dev is not None and self.dim_p == 0:
             ptau_seq_dev = None
+        if plant is not None:
+            li = self._loop_inputs(n_ticks, ptau_seq_dev, per_instance, dist_seq_dev, meas_seq_dev, dist_per_instance,
+                                   meas_per_instance)
+            lr = self._loop_record(n_ticks, **record) if record is not None else None
+            lp = self._loop_plant(plant)
+            _check(load().cgmres_hip_closed_loop_device_plant(self._h, xp, up, int(n_ticks), C.byref(li),
+                                                              C.byref(lr) if lr is not None else None, C.byref(lp)))
+            return
         if record is not None:
             li = self._loop_inputs(n_ticks, ptau_seq_dev, per_instance, dist_seq_dev, meas_seq_dev, dist_per_instance,
                                    meas_per_instance)
@@ -467,6 +512,31 @@ class CgmresBatch:
         li = self._loop_inputs(n_ticks, ptau_seq_dev, per_instance, dist_seq_dev, meas_seq_dev, dist_per_instance,
                                meas_per_instance)
         _check(load().cgmres_hip_closed_loop_device_ex(self._h, xp, up, int(n_ticks), C.byref(li)))
+
+    # -- a plant of its own ----------------------------------------------------------------------------
+    def _loop_plant(self, plant):
+        """struct cgmres_hip_loop_plant of a Plant; a typed theta buffer is checked for element type and count (one row or
+        one row per instance) before its address crosses the ABI."""
+        integ = plant.integrator
+        lp = LoopPlant(struct_size=C.sizeof(LoopPlant), substeps=int(plant.substeps),
+                       integrator=PLANT_INTEGRATORS[integ] if isinstance(integ, str) else int(integ))
+        th = plant.theta
+        if th is not None:
+            n_theta = plant_info(self.model)["n_theta"]
+            numel = int(np.prod(th.shape)) if hasattr(th, "shape") else None
+            per = numel is not None and numel == self.batch * n_theta and (self.batch > 1 or len(th.shape) > 1)
+            if plant.theta_per_instance is not None:
+                per = bool(plant.theta_per_instance)
+            lp.theta_per_instance = 1 if per else 0
+            lp.theta_dev = _ptr(th, self.np_dtype, None if numel is None or n_theta == 0 else (self.batch if per else 1) * n_theta)
+        return lp
+
+    def plant_step_device(self, x_dev, u_dev, plant):
+        """One plant step on the stream, x_dev <- Phi(x_dev, u_dev) with the Plant's integrator, substeps and theta; no d,
+        no v, no controller state changes (cgmres_hip_plant_step_device)."""
+        lp = self._loop_plant(plant)
+        _check(load().cgmres_hip_plant_step_device(self._h, _ptr(x_dev, self.np_dtype, self.batch * self.dim_x),
+                                                   _ptr(u_dev, self.np_dtype, self.batch * self.dim_u), C.byref(lp)))
 
     # -- the record of a closed loop and the ensemble of a batch ----------------------------------------
     def _loop_record(self, n_ticks, stride=1, x=None, u=None, n_ax=None, reason=None, t=None, centre=None, moments=None,
@@ -501,11 +571,12 @@ class CgmresBatch:
                                                  _ptr(u_dev, self.np_dtype, self.batch * self.dim_u), C.byref(out)))
 
     def closed_loop_record(self, x, n_ticks, stride=1, centre=None, u=None, ptau_seq=None, per_instance=True, dist_seq=None,
-                           meas_seq=None, dist_per_instance=True, meas_per_instance=True):
+                           meas_seq=None, dist_per_instance=True, meas_per_instance=True, plant=None):
         """The convenience form: n_ticks of the device loop from the host state x [batch, dim_x], every stride-th tick
         recorded; the sequences are host arrays.  Allocates, runs, synchronises and returns numpy arrays:
         dict(t [n_rec], x [n_rec, batch, dim_x], u [n_rec, batch, dim_u], n_ax, reason [n_rec, batch],
-        moments [n_rec, dim_x+dim_u, 4], counts [n_rec, k_max+7], x_end, u_end)."""
+        moments [n_rec, dim_x+dim_u, 4], counts [n_rec, k_max+7], x_end, u_end).  plant: a Plant whose theta, if any, is a HOST
+        array [batch, n_theta] or [n_theta]."""
         n_ticks, stride = int(n_ticks), int(stride)
         n_rec, nc, B = n_ticks // stride, self.dim_x + self.dim_u, self.batch
         bufs = []
@@ -528,10 +599,14 @@ class CgmresBatch:
                        n_ax=dev((n_rec, B), np.int32), reason=dev((n_rec, B), np.int32), t=t,
                        centre=None if centre is None else dev((nc,), np.float64, np.asarray(centre, dtype=np.float64)),
                        moments=dev((n_rec, nc, 4), np.float64), counts=dev((n_rec, self.k_max + 7), np.int32))
+            if plant is not None and plant.theta is not None and isinstance(plant.theta, (np.ndarray, list, tuple)):
+                th = np.asarray(plant.theta, dtype=self.np_dtype)
+                plant = Plant(plant.integrator, plant.substeps, dev(th.shape, init=th), plant.theta_per_instance)
             self.closed_loop_device(xd, ud, n_ticks, seq(ptau_seq, per_instance, self.dim_p * (self.dv + 1)) if self.dim_p else None,
                                     per_instance, dist_seq_dev=seq(dist_seq, dist_per_instance, self.dim_x),
                                     meas_seq_dev=seq(meas_seq, meas_per_instance, self.dim_x),
-                                    dist_per_instance=dist_per_instance, meas_per_instance=meas_per_instance, record=rec)
+                                    dist_per_instance=dist_per_instance, meas_per_instance=meas_per_instance, record=rec,
+                                    plant=plant)
             out = {k: rec[k].download() for k in ("x", "u", "n_ax", "reason", "moments", "counts")}  # (blocks on the stream)
             out.update(t=t, x_end=xd.download(), u_end=ud.download())
             return out

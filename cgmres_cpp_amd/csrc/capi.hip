@@ -33,6 +33,7 @@ struct Plugin {
   const char* (*last_error)(void);
   cgm::HorizonFn* horizon;  // optional symbol: null in a plugin built before cgmres_hip_horizon_device existed
   int32_t (*record)(void);  // optional symbol: null in a plugin whose contexts predate the record kernels (status_dev)
+  cgm::PlantFn* plant;      // optional symbol: null in a plugin built before cgmres_hip_closed_loop_device_plant existed
 };
 std::deque<Plugin>& plugins() {  // deque: find_plugin hands out pointers that must survive later push_backs
   static std::deque<Plugin> v;
@@ -122,19 +123,22 @@ struct Builtin {
   cgmres_hip_ctx* (*make_f64)(const cgmres_hip_config&, int*);
   cgmres_hip_ctx* (*make_f32)(const cgmres_hip_config&, int*);
   cgm::HorizonFn *horizon_f64, *horizon_f32;  // cgmres_hip_horizon_device on a context that factory made
+  cgm::PlantFn *plant_f64, *plant_f32;        // one launch of the plant kernel on such a context
 };
 template <class F>
 bool with_builtin(int id, F&& f) {
   switch (id) {
     case CGMRES_HIP_MODEL_PENDULUM:
-      f(Builtin<cgm::PendulumDev>{cgm::make_pendulum_f64, cgm::make_pendulum_f32, cgm::horizon_pendulum_f64, cgm::horizon_pendulum_f32});
+      f(Builtin<cgm::PendulumDev>{cgm::make_pendulum_f64, cgm::make_pendulum_f32, cgm::horizon_pendulum_f64, cgm::horizon_pendulum_f32,
+                                    cgm::plant_pendulum_f64, cgm::plant_pendulum_f32});
       return true;
     case CGMRES_HIP_MODEL_MSD:
-      f(Builtin<cgm::MsdDev>{cgm::make_msd_f64, cgm::make_msd_f32, cgm::horizon_msd_f64, cgm::horizon_msd_f32});
+      f(Builtin<cgm::MsdDev>{cgm::make_msd_f64, cgm::make_msd_f32, cgm::horizon_msd_f64, cgm::horizon_msd_f32, cgm::plant_msd_f64,
+                               cgm::plant_msd_f32});
       return true;
     case CGMRES_HIP_MODEL_SEMIACTIVE:
       f(Builtin<cgm::SemiactiveDev>{cgm::make_semiactive_f64, cgm::make_semiactive_f32, cgm::horizon_semiactive_f64,
-                                     cgm::horizon_semiactive_f32});
+                                     cgm::horizon_semiactive_f32, cgm::plant_semiactive_f64, cgm::plant_semiactive_f32});
       return true;
   }
   return false;
@@ -239,6 +243,60 @@ int plugin_records(cgmres_hip_handle h, const char* who) {
   if (pl && !pl->record)
     return fail(CGMRES_HIP_EINVAL, "%s: the plugin %s was built before this entry point existed: rebuild it", who, pl->path.c_str());
   return 0;
+}
+
+// The plant parameters of a model: their number and nominal values (0 for a user model); false for an unknown id
+bool plant_theta_of(int id, int* n_theta, const double** nominal) {
+  *n_theta = 0, *nominal = nullptr;
+  if (find_plugin(id)) return true;
+  return with_builtin(id, [&](auto m) {
+    using Dev = typename decltype(m)::Dev;
+    *n_theta = Dev::NTHETA, *nominal = Dev::theta_nominal;
+  });
+}
+
+// A cgmres_hip_loop_plant, checked; on success the plant fields of *sq are set (plant_step: the model's launch function)
+int plant_check(cgmres_hip_handle h, const char* who, const cgmres_hip_loop_plant* pl, cgm::LoopSeqs* sq) {
+  if (pl->struct_size != int32_t(sizeof(cgmres_hip_loop_plant)))
+    return fail(CGMRES_HIP_EINVAL, "%s: struct_size %d, this library's cgmres_hip_loop_plant has %d", who, pl->struct_size,
+                int(sizeof(cgmres_hip_loop_plant)));
+  if (pl->reserved[0] != 0 || pl->reserved[1] != 0)
+    return fail(CGMRES_HIP_EINVAL, "%s: cgmres_hip_loop_plant.reserved must be 0 (got %d, %d)", who, pl->reserved[0], pl->reserved[1]);
+  if (pl->integrator != CGMRES_HIP_PLANT_EULER && pl->integrator != CGMRES_HIP_PLANT_RK4)
+    return fail(CGMRES_HIP_EINVAL, "%s: unknown integrator %d (CGMRES_HIP_PLANT_EULER = 0, CGMRES_HIP_PLANT_RK4 = 1)", who, pl->integrator);
+  if (pl->substeps < 1 || pl->substeps > 4096) return fail(CGMRES_HIP_EINVAL, "%s: substeps %d outside 1 .. 4096", who, pl->substeps);
+  if (pl->theta_per_instance != 0 && pl->theta_per_instance != 1)
+    return fail(CGMRES_HIP_EINVAL, "%s: theta_per_instance is %d, not 0 or 1", who, pl->theta_per_instance);
+  int n_theta = 0;
+  const double* nominal = nullptr;
+  plant_theta_of(h->cfg.model_id, &n_theta, &nominal);
+  if (pl->theta_dev && n_theta == 0)
+    return fail(CGMRES_HIP_EINVAL, "%s: theta_dev given, but model %d has no plant parameters (n_theta = 0)", who, h->cfg.model_id);
+  cgm::PlantFn* fn = nullptr;
+  if (const Plugin* p = find_plugin(h->cfg.model_id)) {
+    if (!p->plant)
+      return fail(CGMRES_HIP_EINVAL, "%s: the plugin %s was built before this entry point existed: rebuild it", who, p->path.c_str());
+    fn = p->plant;
+  } else {
+    with_builtin(h->cfg.model_id, [&](auto m) { fn = h->cfg.dtype == CGMRES_HIP_F32 ? m.plant_f32 : m.plant_f64; });
+  }
+  if (!fn) return fail(CGMRES_HIP_EINVAL, "%s: unknown model_id %d", who, h->cfg.model_id);
+  sq->plant_step = fn, sq->plant_integrator = pl->integrator, sq->plant_substeps = pl->substeps;
+  sq->plant_theta = pl->theta_dev, sq->plant_theta_inst = pl->theta_dev && pl->theta_per_instance ? n_theta : 0;
+  return 0;
+}
+// bytes of the theta array of a checked plant
+size_t plant_theta_bytes(cgmres_hip_handle h, const cgmres_hip_loop_plant* pl) {
+  int n_theta = 0;
+  const double* nominal = nullptr;
+  plant_theta_of(h->cfg.model_id, &n_theta, &nominal);
+  return size_t(pl->theta_per_instance ? h->cfg.batch : 1) * n_theta * (h->cfg.dtype == CGMRES_HIP_F32 ? 4 : 8);
+}
+// a plugin reports its failures through its own copy of the error string
+int plant_rc(cgmres_hip_handle h, int rc) {
+  if (rc)
+    if (const Plugin* p = find_plugin(h->cfg.model_id)) cgm::g_err = p->last_error();
+  return rc;
 }
 
 __global__ void sincos_selftest_kernel(const double* a, double* s, double* c, int n) {
@@ -351,7 +409,7 @@ int cgmres_hip_register_model(const char* plugin_path, int32_t* model_id) {
   const int rc = open_plugin(
       plugins(), "model", "cgmres_hip_plugin_", plugin_path, model_id ? &n : nullptr, pl,
       {{"info", &info, true}, {"make", &pl.make, true}, {"probe", &pl.probe, true}, {"last_error", &pl.last_error, true},
-       {"horizon", &pl.horizon, false}, {"record", &pl.record, false}},
+       {"horizon", &pl.horizon, false}, {"record", &pl.record, false}, {"plant", &pl.plant, false}},
       [&](Plugin& q) {
         int32_t dims[5];
         double tun[6];
@@ -547,10 +605,37 @@ int cgmres_hip_ensemble_device(cgmres_hip_handle h, const void* x, const void* u
 }
 int cgmres_hip_closed_loop_device_rec(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const cgmres_hip_loop_inputs* in,
                                       const cgmres_hip_loop_record* rec) {
+  return cgmres_hip_closed_loop_device_plant(h, x, u, n_ticks, in, rec, nullptr);
+}
+int cgmres_hip_closed_loop_device_plant(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const cgmres_hip_loop_inputs* in,
+                                        const cgmres_hip_loop_record* rec, const cgmres_hip_loop_plant* plant) {
   NEED(h);
   cgm::LoopSeqs sq;
   if (int rc = loop_seqs(h, x, u, n_ticks, in, &sq)) return rc;
-  if (!rec) return closed_loop(h, x, u, n_ticks, sq);
+  struct Range { const char* name; const void* p; size_t bytes; };
+  auto overlap = [](const Range& a, const Range& b) {
+    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a.p), pb = reinterpret_cast<uintptr_t>(b.p);
+    return pa < pb + b.bytes && pb < pa + a.bytes;
+  };
+  const size_t es = h->cfg.dtype == CGMRES_HIP_F32 ? 4 : 8, B = size_t(h->cfg.batch), seq_rows = size_t(n_ticks);
+  const size_t nc = size_t(h->nx + h->nu);
+  Range theta{"theta_dev", nullptr, 0};
+  if (plant) {
+    if (int rc = plant_check(h, "closed_loop_device_plant", plant, &sq)) return rc;
+    theta = {"theta_dev", plant->theta_dev, plant_theta_bytes(h, plant)};
+    // the alias guard, extended: theta shares no byte with x_dev, u_dev or an input sequence (the logs: below)
+    const Range io[5] = {{"x_dev", x, B * h->nx * es},
+                         {"u_dev", u, B * h->nu * es},
+                         {"ptau_seq_dev", sq.ptau, seq_rows * (sq.ptau_per_instance ? B : 1) * h->np * (h->cfg.dv + 1) * es},
+                         {"dist_seq_dev", sq.dist, seq_rows * (sq.dist_per_instance ? B : 1) * h->nx * es},
+                         {"meas_seq_dev", sq.meas, seq_rows * (sq.meas_per_instance ? B : 1) * h->nx * es}};
+    for (const Range& o : io)
+      if (overlap(theta, o))
+        return fail(CGMRES_HIP_EINVAL, "closed_loop_device_plant: theta_dev overlaps %s (cgmres.hpp DEBUG_MODE alias guard)", o.name);
+  }
+  auto run = [&] { return plant ? plant_rc(h, closed_loop(h, x, u, n_ticks, sq)) : closed_loop(h, x, u, n_ticks, sq); };
+  if (!rec) return run();
   if (rec->struct_size != int32_t(sizeof(cgmres_hip_loop_record)))
     return fail(CGMRES_HIP_EINVAL, "closed_loop_device_rec: struct_size %d, this library's cgmres_hip_loop_record has %d",
                 rec->struct_size, int(sizeof(cgmres_hip_loop_record)));
@@ -562,25 +647,19 @@ int cgmres_hip_closed_loop_device_rec(cgmres_hip_handle h, void* x, void* u, int
   if (!u) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_rec: null u_dev");
   if (!rec->x_log_dev && !rec->u_log_dev && !rec->n_ax_log_dev && !rec->reason_log_dev && !rec->t_host && !rec->moments_log_dev &&
       !rec->counts_log_dev)
-    return closed_loop(h, x, u, n_ticks, sq);
-  // the alias guard of ..._ex, extended: a log shares no byte with x_dev, u_dev, another log or an input sequence
-  const size_t es = h->cfg.dtype == CGMRES_HIP_F32 ? 4 : 8, B = size_t(h->cfg.batch), n_rec = size_t(n_ticks / rec->stride);
-  const size_t nc = size_t(h->nx + h->nu), seq_rows = size_t(n_ticks);
-  struct Range { const char* name; const void* p; size_t bytes; };
+    return run();
+  // the alias guard of ..._ex, extended: a log shares no byte with x_dev, u_dev, another log, an input sequence or theta
+  const size_t n_rec = size_t(n_ticks / rec->stride);
   const Range logs[6] = {{"x_log_dev", rec->x_log_dev, n_rec * B * h->nx * es},       {"u_log_dev", rec->u_log_dev, n_rec * B * h->nu * es},
                          {"n_ax_log_dev", rec->n_ax_log_dev, n_rec * B * 4},          {"reason_log_dev", rec->reason_log_dev, n_rec * B * 4},
                          {"moments_log_dev", rec->moments_log_dev, n_rec * nc * 32}, {"counts_log_dev", rec->counts_log_dev, n_rec * size_t(h->cfg.k_max + 7) * 4}};
-  const Range others[6] = {{"x_dev", x, B * h->nx * es},
+  const Range others[7] = {{"x_dev", x, B * h->nx * es},
                            {"u_dev", u, B * h->nu * es},
                            {"ptau_seq_dev", sq.ptau, seq_rows * (sq.ptau_per_instance ? B : 1) * h->np * (h->cfg.dv + 1) * es},
                            {"dist_seq_dev", sq.dist, seq_rows * (sq.dist_per_instance ? B : 1) * h->nx * es},
                            {"meas_seq_dev", sq.meas, seq_rows * (sq.meas_per_instance ? B : 1) * h->nx * es},
-                           {"centre_dev", rec->centre_dev, nc * 8}};
-  auto overlap = [](const Range& a, const Range& b) {
-    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a.p), pb = reinterpret_cast<uintptr_t>(b.p);
-    return pa < pb + b.bytes && pb < pa + a.bytes;
-  };
+                           {"centre_dev", rec->centre_dev, nc * 8},
+                           theta};
   for (int i = 0; i < 6; ++i) {
     for (const Range& o : others)
       if (overlap(logs[i], o)) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_rec: %s overlaps %s (cgmres.hpp DEBUG_MODE alias guard)", logs[i].name, o.name);
@@ -589,7 +668,38 @@ int cgmres_hip_closed_loop_device_rec(cgmres_hip_handle h, void* x, void* u, int
   }
   if (int rc = plugin_records(h, "closed_loop_device_rec")) return rc;
   sq.rec_stride = rec->stride, sq.rec_take = take_loop_record, sq.rec = const_cast<cgmres_hip_loop_record*>(rec);
-  return closed_loop(h, x, u, n_ticks, sq);
+  return run();
+}
+int cgmres_hip_plant_info(int32_t model_id, int32_t* n_theta, double* nominal, int32_t cap) {
+  int n = 0;
+  const double* nom = nullptr;
+  if (!plant_theta_of(model_id, &n, &nom)) return fail(CGMRES_HIP_EINVAL, "unknown model_id %d", model_id);
+  if (n_theta) *n_theta = n;
+  if (nominal) {
+    if (cap < n) return fail(CGMRES_HIP_EINVAL, "plant_info: model %d has %d plant parameters, cap = %d", model_id, n, cap);
+    for (int i = 0; i < n; ++i) nominal[i] = nom[i];
+  }
+  return 0;
+}
+int cgmres_hip_plant_step_device(cgmres_hip_handle h, void* x, const void* u, const cgmres_hip_loop_plant* plant) {
+  NEED(h);
+  if (!plant) return fail(CGMRES_HIP_EINVAL, "plant_step_device: null plant");
+  if (!x) return fail(CGMRES_HIP_EINVAL, "plant_step_device: null x_dev");
+  if (!u) return fail(CGMRES_HIP_EINVAL, "plant_step_device: null u_dev");
+  cgm::LoopSeqs sq;
+  if (int rc = plant_check(h, "plant_step_device", plant, &sq)) return rc;
+  const size_t es = h->cfg.dtype == CGMRES_HIP_F32 ? 4 : 8, B = size_t(h->cfg.batch), tb = plant_theta_bytes(h, plant);
+  auto overlaps = [&](const void* o, size_t bytes) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(plant->theta_dev), b = reinterpret_cast<uintptr_t>(o);
+    return plant->theta_dev && tb && a < b + bytes && b < a + tb;
+  };
+  if (overlaps(x, B * h->nx * es)) return fail(CGMRES_HIP_EINVAL, "plant_step_device: theta_dev overlaps x_dev (cgmres.hpp DEBUG_MODE alias guard)");
+  if (overlaps(u, B * h->nu * es)) return fail(CGMRES_HIP_EINVAL, "plant_step_device: theta_dev overlaps u_dev (cgmres.hpp DEBUG_MODE alias guard)");
+  ENTER(h);
+  cgm::PlantCall c;
+  c.x = x, c.u = u, c.theta = sq.plant_theta, c.theta_inst = sq.plant_theta_inst;
+  c.integrator = sq.plant_integrator, c.substeps = sq.plant_substeps;
+  return plant_rc(h, sq.plant_step(h, c));
 }
 int cgmres_hip_horizon_device(cgmres_hip_handle h, const void* x, const cgmres_hip_horizon_out* out) {
   NEED(h);

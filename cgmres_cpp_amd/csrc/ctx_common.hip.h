@@ -39,6 +39,24 @@ inline int fail(int code, const char* fmt, ...) {
 
 struct cgmres_hip_ctx;
 namespace cgm {
+// One launch of plant_kernel (plant.hip.h) on a context's stream: device pointers in the handle's dtype, caller order.
+// The context that runs a loop fills p (stage 0 of the horizon its tick was given, in its own layout); a null p is filled
+// from the handle's ptau by who knows the context's concrete type (factory_impl.hip.h: plant_variant).
+struct PlantCall {
+  void* x = nullptr;        // [B][nx] in/out
+  const void* u = nullptr;  // [B][nu]
+  const void* theta = nullptr;  // [B or 1][n_theta]; null = nominal
+  int theta_inst = 0;           // n_theta per instance, 0 for one broadcast row
+  const void* p = nullptr;      // element j of instance b at p[b * p_inst + j * p_elem]
+  size_t p_inst = 0, p_elem = 0;
+  const void* d = nullptr;  // this tick's rows, [nx] at b * d_inst; null = absent
+  int d_inst = 0;
+  const void* v = nullptr;  // the NEXT tick's rows
+  int v_inst = 0;
+  void* y = nullptr;     // [B][nx] = x + v; null = not wanted
+  int integrator = 0;    // CGMRES_HIP_PLANT_*
+  int substeps = 1;      // 0: measure only (y = x + v, x untouched)
+};
 // Per-tick input sequences of the closed loop (cgmres_hip_loop_inputs, validated by capi.hip): device pointers,
 // [n_ticks][batch or 1][...]; null = absent
 struct LoopSeqs {
@@ -56,6 +74,13 @@ struct LoopSeqs {
   int (*rec_take)(void* rec, cgmres_hip_ctx* c, int j, const void* x, const void* u, const int32_t* n_ax,
                   const int32_t* reason, double t) = nullptr;
   void* rec = nullptr;
+  // The plant of cgmres_hip_closed_loop_device_plant (plant.hip.h): null plant_step = the fused plant block of the tick
+  // kernels.  A context that is given one cuts to one tick per launch, launches the tick without a plant step and calls
+  // plant_step behind it.  A pointer like rec_take: for a user model the function lives in its plugin.
+  int (*plant_step)(cgmres_hip_ctx* c, const PlantCall& call) = nullptr;
+  int plant_integrator = 0, plant_substeps = 1;
+  const void* plant_theta = nullptr;
+  int plant_theta_inst = 0;
 };
 }  // namespace cgm
 

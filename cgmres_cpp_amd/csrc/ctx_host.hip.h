@@ -122,6 +122,23 @@ struct CtxHost : cgmres_hip_ctx {
   int record(const LoopSeqs& sq, int j, const void* x, const void* u, T t_tick) {
     return sq.rec_take(sq.rec, this, j, x, u, self().P.n_ax, self().P.reason, double(t_tick));
   }
+  // The plant of a loop that brings its own (LoopSeqs::plant_step), on the stream behind the launch of tick k of n_ticks:
+  // x <- Phi(x, u) + d_k and, while a tick follows, y <- x + v_{k+1}.  p: stage 0 of the horizon tick k was given, in
+  // the mapping's layout.  k = -1: no step, the first tick's measurement y <- x + v_0.
+  T* plant_y = nullptr;  // [B][nx], grown on demand: what the controller is shown when v is given
+  size_t plant_y_n = 0;
+  int plant_tick(const LoopSeqs& sq, int k, int n_ticks, void* x, const void* u, HorizonView<const T> p) {
+    const T *dseq = static_cast<const T*>(sq.dist), *mseq = static_cast<const T*>(sq.meas);
+    const size_t d_tick = size_t(sq.dist_per_instance ? cfg.batch : 1) * nx, m_tick = size_t(sq.meas_per_instance ? cfg.batch : 1) * nx;
+    PlantCall c;
+    c.x = x, c.u = u;
+    c.theta = sq.plant_theta, c.theta_inst = sq.plant_theta_inst;
+    c.p = p.p, c.p_inst = p.sb, c.p_elem = p.se;
+    c.integrator = sq.plant_integrator, c.substeps = k < 0 ? 0 : sq.plant_substeps;
+    if (k >= 0 && dseq) c.d = dseq + size_t(k) * d_tick, c.d_inst = sq.dist_per_instance ? nx : 0;
+    if (mseq && k + 1 < n_ticks) c.v = mseq + size_t(k + 1) * m_tick, c.v_inst = sq.meas_per_instance ? nx : 0, c.y = plant_y;
+    return sq.plant_step(this, c);
+  }
 };
 
 }  // namespace cgm

@@ -95,6 +95,15 @@ struct CtxLane final : CtxHost<M, T, CtxLane<M, T>> {
     const size_t d_tick = size_t(sq.dist_per_instance ? cfg.batch : 1) * nx, m_tick = size_t(sq.meas_per_instance ? cfg.batch : 1) * nx;
     P.dist_inst = sq.dist_per_instance ? nx : 0, P.meas_inst = sq.meas_per_instance ? nx : 0;
     int rc = 0;
+    // a loop with a plant of its own (LoopSeqs::plant_step): no plant step and no d / v in the tick kernel; the controller
+    // is shown y = x + v, which the plant kernel leaves in plant_y
+    const bool own_plant = sq.plant_step != nullptr;
+    const T* x_seen = static_cast<const T*>(x);
+    if (own_plant && mseq && n_ticks > 0) {
+      if ((rc = grow(&this->plant_y, &this->plant_y_n, size_t(cfg.batch) * nx))) return rc;
+      x_seen = Host::plant_y;
+    }
+    const HorizonView<const T> p0{P.ptau, 1, size_t(ldb)};  // (the handle's ptau holds this tick's horizon: set below)
     RecordCut cut(n_ticks, sq.rec_take ? sq.rec_stride : 0, 1);  // (one tick per launch: the cut only says where a record is due)
     while (!cut.done() && !rc) {
       const int i = cut.i;
@@ -107,9 +116,15 @@ struct CtxLane final : CtxHost<M, T, CtxLane<M, T>> {
                                                        ldb, all, !per_instance);
         HIP_TRY(hipGetLastError());
       }
-      P.dist = dseq ? dseq + size_t(i) * d_tick : nullptr;
-      P.meas = mseq ? mseq + size_t(i) * m_tick : nullptr;
-      rc = launch_tick(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x));
+      if (own_plant) {
+        if (i == 0 && x_seen != x) rc = Host::plant_tick(sq, -1, n_ticks, x, u, p0);
+        if (!rc) rc = launch_tick(static_cast<T*>(u), x_seen, nullptr);
+        if (!rc) rc = Host::plant_tick(sq, i, n_ticks, x, u, p0);
+      } else {
+        P.dist = dseq ? dseq + size_t(i) * d_tick : nullptr;
+        P.meas = mseq ? mseq + size_t(i) * m_tick : nullptr;
+        rc = launch_tick(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x));
+      }
       if (!rc && rec) rc = Host::record(sq, cut.i / sq.rec_stride - 1, x, u, t_tick);
     }
     P.dist = nullptr, P.meas = nullptr;  // control() and the hooks take neither

@@ -220,12 +220,27 @@ struct CtxWg final : CtxHost<M, T, CtxWg<M, T>> {
     PlantSeqs<T> ps{static_cast<const T*>(sq.dist), static_cast<const T*>(sq.meas),
                     size_t(sq.dist_per_instance ? cfg.batch : 1) * nx, size_t(sq.meas_per_instance ? cfg.batch : 1) * nx,
                     sq.dist_per_instance ? nx : 0, sq.meas_per_instance ? nx : 0};
-    const bool plant_in = ps.dist || ps.meas;
+    // a loop with a plant of its own (LoopSeqs::plant_step): one tick per launch, no plant step in the tick kernel and no
+    // PlantSeqs record; the controller is shown y = x + v, which the plant kernel leaves in plant_y
+    const bool own_plant = sq.plant_step != nullptr;
+    const bool plant_in = !own_plant && (ps.dist || ps.meas);
+    const T* x_seen = static_cast<const T*>(x);
+    if (own_plant && ps.meas && n_ticks > 0) {
+      if (int rc = grow(&this->plant_y, &this->plant_y_n, size_t(cfg.batch) * nx)) return rc;
+      x_seen = Host::plant_y;
+    }
+    // stage 0 of the horizon tick i is given: row i of the sequence, or the handle's ptau
+    auto p_of = [&](int i) {
+      return seq ? HorizonView<const T>{seq + size_t(i) * per_tick, size_t(per_instance ? all : 0), 1}
+                 : HorizonView<const T>{P.ptau, size_t(all), 1};
+    };
     // (a lambda, so that a failed launch check leaves through the line below it, which takes the per-launch pointers off
     // the handle: a later control() must not meet a stale sequence or PlantSeqs record)
     auto launches = [&]() -> int {
       // the launch sizes: today's cut, or with a record the cut of record_plan.hip.h (every recorded tick ends a launch)
-      RecordCut cut(n_ticks, sq.rec_take ? sq.rec_stride : 0, CGM_FUSE_MAX);
+      RecordCut cut(n_ticks, sq.rec_take ? sq.rec_stride : 0, own_plant ? 1 : CGM_FUSE_MAX);
+      if (own_plant && x_seen != x)
+        if (int rp = Host::plant_tick(sq, -1, n_ticks, x, u, p_of(0))) return rp;
       while (!cut.done()) {
         const int i = cut.i;
         bool rec = false;
@@ -246,10 +261,12 @@ struct CtxWg final : CtxHost<M, T, CtxWg<M, T>> {
         }
         T t_last = t;  // the time of the launch's last control(), by the statements of launch_ticks
         for (int k = 1; k < n; ++k) t_last = t_last + P.dt;
-        const int rc = launch_ticks(static_cast<T*>(u), static_cast<const T*>(x), static_cast<T*>(x), n);
+        const int rc = launch_ticks(static_cast<T*>(u), x_seen, own_plant ? nullptr : static_cast<T*>(x), n);
         P.perm = nullptr;
         have_counts = true;
         if (rc) return rc;
+        if (own_plant)
+          if (int rp = Host::plant_tick(sq, i, n_ticks, x, u, p_of(i))) return rp;
         if (rec)
           if (int rr = Host::record(sq, cut.i / sq.rec_stride - 1, x, u, t_last)) return rr;
       }

@@ -16,6 +16,9 @@ cgmres_hip_ctx* make_semiactive_f64(const cgmres_hip_config& cfg, int* resolved)
 cgmres_hip_ctx* make_semiactive_f32(const cgmres_hip_config& cfg, int* resolved);
 HorizonFn horizon_pendulum_f64, horizon_pendulum_f32, horizon_msd_f64, horizon_msd_f32, horizon_semiactive_f64,
     horizon_semiactive_f32;
+// plant_* = one launch of the plant kernel (plant.hip.h, factory_impl.hip.h: plant_variant), all six in inst_plant.hip.
+using PlantFn = int(cgmres_hip_ctx*, const PlantCall& call);
+PlantFn plant_pendulum_f64, plant_pendulum_f32, plant_msd_f64, plant_msd_f32, plant_semiactive_f64, plant_semiactive_f32;
 // One record of a closed loop / the ensemble of a batch (record.hip.h), on the context's stream: the log rows and the
 // statistics of x [batch][nx], u [batch][nu] and the status arrays given; any destination may be null.  Independent of
 // model and mapping, so there is one function, in inst_record.hip.

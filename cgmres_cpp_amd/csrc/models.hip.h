@@ -285,6 +285,18 @@ struct PendulumDev {
     f[2] = -As * x[2] + Bs * u[0];
     f[3] = A32 * x[2] * x[2] * sd + A52 * s1 - A32b * cd * u[0] + A32a * cd * x[2] + C22 * (x[2] - x[3]);
   }
+  // The plant parameters (plant.hip.h): the constants dxdt reads, and dxdt with th[] in their place
+  static constexpr int NTHETA = 7;
+  static constexpr T theta_nominal[NTHETA] = {As, Bs, A52, C22, A32a, A32, A32b};
+  template <class MC>
+  static __device__ __forceinline__ void dxdt_theta(T* f, const T* x, const T* u, const T* th, const MC& mc) {
+    T sd, cd, s1, c1;
+    mc.sincos_pair(x[0] - x[1], x[1], &sd, &cd, &s1, &c1);
+    f[0] = x[2];
+    f[1] = x[3];
+    f[2] = -th[0] * x[2] + th[1] * u[0];
+    f[3] = th[5] * x[2] * x[2] * sd + th[2] * s1 - th[6] * cd * u[0] + th[4] * cd * x[2] + th[3] * (x[2] - x[3]);
+  }
   static __device__ __forceinline__ void dPhidx(T* g, const T* x, const T* p) {  // model.hpp:44-49
     g[0] = (x[0] - p[0]) * sf0;
     g[1] = (x[1] - p[1]) * sf1;
@@ -553,6 +565,16 @@ struct MsdDev {
     f[2] = -(k1 * k2) / m1 * x[0] + k2 / m1 * x[1] - (d1 + d2) / m1 * x[2] + d2 / m1 * x[3] + u[0] / m1;
     f[3] = k2 / m2 * x[0] - k2 / m2 * x[1] + d2 / m2 * x[2] - d2 / m2 * x[3] + u[1] / m2;
   }
+  // The plant parameters (plant.hip.h): th = {m1, m2, d1, d2, k1, k2}, the (k1*k2) form of dxdt kept
+  static constexpr int NTHETA = 6;
+  static constexpr T theta_nominal[NTHETA] = {m1, m2, d1, d2, k1, k2};
+  static __device__ __forceinline__ void dxdt_theta(T* f, const T* x, const T* u, const T* th, const Math&) {
+    const T pm1 = th[0], pm2 = th[1], pd1 = th[2], pd2 = th[3], pk1 = th[4], pk2 = th[5];
+    f[0] = x[2];
+    f[1] = x[3];
+    f[2] = -(pk1 * pk2) / pm1 * x[0] + pk2 / pm1 * x[1] - (pd1 + pd2) / pm1 * x[2] + pd2 / pm1 * x[3] + u[0] / pm1;
+    f[3] = pk2 / pm2 * x[0] - pk2 / pm2 * x[1] + pd2 / pm2 * x[2] - pd2 / pm2 * x[3] + u[1] / pm2;
+  }
   static __device__ __forceinline__ void dPhidx(T* g, const T* x, const T* p) {  // model.hpp:43-48
     g[0] = -(p[0] - x[0]) * sf0;
     g[1] = -(p[1] - x[1]) * sf1;
@@ -637,6 +659,13 @@ struct SemiactiveDev {
   static __device__ __forceinline__ void dxdt(T* f, const T* x, const T* u, T*, const Math&) {  // model.hpp:36-39
     f[0] = x[1];
     f[1] = a * x[0] + b * u[0] * x[1];
+  }
+  // The plant parameters (plant.hip.h): th = {a, b}
+  static constexpr int NTHETA = 2;
+  static constexpr T theta_nominal[NTHETA] = {a, b};
+  static __device__ __forceinline__ void dxdt_theta(T* f, const T* x, const T* u, const T* th, const Math&) {
+    f[0] = x[1];
+    f[1] = th[0] * x[0] + th[1] * u[0] * x[1];
   }
   static __device__ __forceinline__ void dPhidx(T* g, const T* x, const T*) {  // model.hpp:41-44
     g[0] = x[0] * sf0;

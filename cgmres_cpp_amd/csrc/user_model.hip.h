@@ -32,6 +32,7 @@ template <class Model>
 struct UserDev {
   static constexpr int NX = Model::dim_x, NU = Model::dim_u, NP = Model::dim_p, NC = 0, NU_DYN = Model::dim_u;
   static constexpr bool DXDT_USES_P = true;
+  static constexpr int NTHETA = 0;  // no plant parameters (plant.hip.h): a user model's plant is its own dxdt(x, u, p)
   using Math = NoConsts;
   template <bool>
   using MathFor = NoConsts;
@@ -222,7 +223,20 @@ extern "C" int cgmres_hip_plugin_debug_lds_oob(void) {
   int32_t cgmres_hip_plugin_record(void) { return 1; }
 #endif
 
-// The entry points of a model plugin (bound by cgmres_hip_register_model in capi.hip): four required, horizon and record optional.
+// The third optional entry point: one launch of plant_kernel<UserDev<MODEL>> on a context cgmres_hip_plugin_make made
+// (cgmres_hip_plant_step_device, cgmres_hip_closed_loop_device_plant).  The library refuses those two calls, and nothing
+// else, for a plugin without it, which the tests imitate with -DCGM_PLUGIN_WITHOUT_PLANT.
+#ifdef CGM_PLUGIN_WITHOUT_PLANT
+#define CGM_PLUGIN_PLANT(MODEL)
+#else
+#define CGM_PLUGIN_PLANT(MODEL)                                                   \
+  int cgmres_hip_plugin_plant(cgmres_hip_ctx* c, const cgm::PlantCall& call) {    \
+    return cgm::plant_variant<cgm::UserDev<MODEL>, double>(c, call);              \
+  }
+#endif
+
+// The entry points of a model plugin (bound by cgmres_hip_register_model in capi.hip): four required, horizon, record and
+// plant optional.
 #define CGMRES_HIP_DEFINE_PLUGIN(MODEL)                                                                          \
   extern "C" {                                                                                                   \
   int32_t cgmres_hip_plugin_abi(void) { return CGMRES_HIP_ABI_VERSION; }                                         \
@@ -258,4 +272,5 @@ extern "C" int cgmres_hip_plugin_debug_lds_oob(void) {
   const char* cgmres_hip_plugin_last_error(void) { return cgm::g_err.c_str(); }                                  \
   CGM_PLUGIN_HORIZON(MODEL)                                                                                      \
   CGM_PLUGIN_RECORD                                                                                              \
+  CGM_PLUGIN_PLANT(MODEL)                                                                                        \
   }

@@ -7,6 +7,9 @@
 //   ... --device-loop                              (the four above, anywhere on the line) the loop runs in ONE call of
 //                                                  the device-resident closed loop with a stride-1 record, and the two
 //                                                  files are written from its logs: same lines, no host call per tick
+//   ... --device-loop --plant euler|rk4:N          the device loop against a plant of its own: N substeps of dt/N of forward
+//                                                  Euler or RK4 on the model's state equation, nominal parameters
+//                                                  (cgmres_hip_closed_loop_device_plant; euler:1 is the mains' plant)
 //   closed_loop batch <B>  [ticks]                B perturbed pendulum controllers, dv=50, k_max=10, CgmresBatch
 //   closed_loop sharded <B> <dev,dev,...> [ticks]  the same batch owned shard by shard on the listed devices
 //                                                  (CgmresBatchSharded; a device may be listed twice), checked against
@@ -81,6 +84,7 @@ static const double kMsdX0[4] = {2.0, 2.0, 0.0, 0.0}, kMsdU0[6] = {0.0, 0.0, 10.
 static const double kSemiX0[2] = {2.0, 0.0}, kSemiU0[3] = {0.028393761456740, 0.166095020295846, 0.030103250483332};
 
 static bool g_device_loop = false;  // --device-loop
+static cgmres_hip_loop_plant g_plant = {};  // --plant euler|rk4:N (struct_size 0: none given)
 template <class Model>
 static int run_single_device(const char* prefix, int ticks, const double* x0, const double* u0, const double* p);
 
@@ -133,7 +137,10 @@ struct DeviceLoop {
     cgmres_hip_loop_record rec = {};
     rec.struct_size = int32_t(sizeof rec), rec.stride = 1;
     rec.x_log_dev = x_log, rec.u_log_dev = u_log, rec.t_host = t.data();
-    controller.closed_loop_device(x_dev, u_dev, ticks, nullptr, rec);
+    if (g_plant.struct_size)
+      controller.closed_loop_device(x_dev, u_dev, ticks, nullptr, &rec, g_plant);
+    else
+      controller.closed_loop_device(x_dev, u_dev, ticks, nullptr, rec);
   }
   void write_files() {
     const cgmres_hip_handle h = controller.native_handle();
@@ -311,7 +318,27 @@ int main(int argc, char** argv) {
       g_device_loop = true;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc, --i;
+    } else if (!strcmp(argv[i], "--plant") && i + 1 < argc) {  // euler | rk4, optionally :N substeps
+      const char* spec = argv[i + 1];
+      const char* colon = strchr(spec, ':');
+      const size_t len = colon ? size_t(colon - spec) : strlen(spec);
+      g_plant.struct_size = int32_t(sizeof g_plant);
+      g_plant.substeps = colon ? atoi(colon + 1) : 1;
+      if (len == 3 && !strncmp(spec, "rk4", 3)) {
+        g_plant.integrator = CGMRES_HIP_PLANT_RK4;
+      } else if (len == 5 && !strncmp(spec, "euler", 5)) {
+        g_plant.integrator = CGMRES_HIP_PLANT_EULER;
+      } else {
+        fprintf(stderr, "--plant %s: euler|rk4[:N] expected\n", spec);
+        return 1;
+      }
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2, --i;
     }
+  if (g_plant.struct_size && !g_device_loop) {
+    fprintf(stderr, "--plant needs --device-loop\n");
+    return 1;
+  }
   const char* which = argc > 1 ? argv[1] : "pendulum";
   if (!strcmp(which, "batch")) return run_batch(argc > 2 ? atoi(argv[2]) : 4096, argc > 3 ? atoi(argv[3]) : 100);
   if (!strcmp(which, "sharded"))
@@ -328,6 +355,6 @@ int main(int argc, char** argv) {
     return run_single<examples::SemiactiveModel<50, 5>, examples::SemiactivePlant>(
         prefix ? prefix : "semiactive_damper", ticks < 0 ? 20001 : ticks, kSemiX0, kSemiU0, kSemiX0 /*unused: dim_p = 0*/);
   if (!strcmp(which, "multiple")) return run_multiple(prefix ? prefix : "multiple_controller_", ticks < 0 ? 10001 : ticks);
-  fprintf(stderr, "usage: %s pendulum|msd|semiactive|multiple [ticks] [prefix] [--device-loop]  |  batch <B> [ticks]  |  sharded <B> <dev,dev,..> [ticks]\n", argv[0]);
+  fprintf(stderr, "usage: %s pendulum|msd|semiactive|multiple [ticks] [prefix] [--device-loop [--plant euler|rk4:N]]  |  batch <B> [ticks]  |  sharded <B> <dev,dev,..> [ticks]\n", argv[0]);
   return 2;
 }

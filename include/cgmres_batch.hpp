@@ -78,6 +78,17 @@ class CgmresBatch {
                           const cgmres_hip_loop_record& rec) {
     cgmres_detail::check(cgmres_hip_closed_loop_device_rec(handle_, x_dev, u_dev, n_ticks, in, &rec), "closed_loop_device_rec");
   }
+  // the same loop against a plant of its own: x_{k+1} = Phi(x_k, u_k) + d_k, Phi = plant.substeps steps of dt/substeps of
+  // forward Euler or RK4 on the state equation with the parameters plant.theta_dev — cgmres_hip_closed_loop_device_plant.
+  // `in` and `rec` may be null; `plant.struct_size` must be sizeof(cgmres_hip_loop_plant).  One tick per kernel launch
+  void closed_loop_device(double* x_dev, double* u_dev, int32_t n_ticks, const cgmres_hip_loop_inputs* in,
+                          const cgmres_hip_loop_record* rec, const cgmres_hip_loop_plant& plant) {
+    cgmres_detail::check(cgmres_hip_closed_loop_device_plant(handle_, x_dev, u_dev, n_ticks, in, rec, &plant), "closed_loop_device_plant");
+  }
+  // one step of that plant on the stream, x_dev <- Phi(x_dev, u_dev): no d, no v, no controller state changes
+  void plant_step_device(double* x_dev, const double* u_dev, const cgmres_hip_loop_plant& plant) {
+    cgmres_detail::check(cgmres_hip_plant_step_device(handle_, x_dev, u_dev, &plant), "plant_step_device");
+  }
   // mean / spread sums, min, max per component of x_dev, u_dev over the instances whose row is finite, and the counts of
   // the controllers' current status, into the device arrays `out` names — cgmres_hip_ensemble_device.  Asynchronous on
   // the handle's stream; changes no state
@@ -113,7 +124,8 @@ class CgmresBatch {
 // enqueued on every shard's stream and runs concurrently.  `devices` may name a device more than once (two shards on
 // one card: how the tests run it).  The record of a closed loop and the ensemble (CgmresBatch::closed_loop_device with a
 // cgmres_hip_loop_record, ensemble_device) are not offered here: an ensemble over shards needs a combine across devices;
-// shard(r) gives the per-shard calls.
+// shard(r) gives the per-shard calls.  Nor is the loop against a plant of its own (cgmres_hip_loop_plant,
+// plant_step_device): its theta_dev is a per-device array the caller would have to cut along the shards; shard(r) again.
 template <class Model>
 class CgmresBatchSharded {
  public:

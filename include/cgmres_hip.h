@@ -319,6 +319,52 @@ int cgmres_hip_closed_loop_device_rec(cgmres_hip_handle h, void* x_dev, void* u_
  * CGMRES_HIP_EINVAL: n_ticks < 0, stride < 1, cap too small.  Pure host arithmetic: needs no GPU. */
 int cgmres_hip_record_plan(int32_t n_ticks, int32_t stride, int32_t* n_rec, int32_t* launch_ticks, int32_t cap,
                            int32_t* n_launches);
+/* ---- a closed loop against a plant of its own: parameters, RK4, substeps ----------------------------------------------- */
+/* The plant of the loops above is the controller's own model with its compile-time constants, stepped by one forward-Euler
+ * step of dt.  Here the plant is
+ *     Phi(x, u; theta, p) = `substeps` steps of length dt/substeps of forward Euler or classical RK4 on the model's state
+ *                           equation, u, p and theta held over the tick (zero-order hold), computed in the handle's dtype
+ * theta: the constants the state equation reads, as run-time values (cgmres_hip_plant_info gives their number and the
+ * nominal values, in this order):
+ *     pendulum     7   As, Bs, A52, C22, A32a, A32, A32b      (arm_type_inverted_pendulum/model.hpp:80-98)
+ *     MSD          6   m1, m2, d1, d2, k1, k2                 (mass_spring_damper/model.hpp; the (k1*k2) form of dxdt kept)
+ *     semi-active  2   a, b                                   (semiactive_damper/model.hpp:85-86)
+ * theta_dev is a device array of the handle's dtype, [batch][n_theta] (theta_per_instance = 1) or one row [n_theta]
+ * broadcast to every instance (0); NULL = nominal (the model's own dxdt runs).  A user model has n_theta = 0: its plant is
+ * its own dxdt(x, u, p), with p = stage 0 of the horizon the controller was given for that tick (row k of ptau_seq_dev
+ * where a sequence is given, the handle's ptau otherwise).  The plant is a kernel of its own between the tick launches:
+ * the loop runs ONE tick per launch, which is what this entry point costs against the fused loop. */
+enum { CGMRES_HIP_PLANT_EULER = 0, CGMRES_HIP_PLANT_RK4 = 1 };
+typedef struct cgmres_hip_loop_plant {
+  int32_t struct_size;        /* sizeof(cgmres_hip_loop_plant); anything else: CGMRES_HIP_EINVAL */
+  int32_t integrator;         /* CGMRES_HIP_PLANT_* */
+  int32_t substeps;           /* 1 .. 4096 */
+  int32_t theta_per_instance; /* 0 / 1 */
+  const void* theta_dev;      /* handle's dtype; NULL = nominal */
+  int32_t reserved[2];        /* 0 */
+} cgmres_hip_loop_plant;
+/* *n_theta = the number of plant parameters of a model (0 for a user model), nominal[0 .. n_theta) their nominal values
+ * (nominal NULL: only the number is wanted; cap = its capacity).  CGMRES_HIP_EINVAL: an unknown model, cap < n_theta.
+ * Pure host arithmetic: needs no GPU. */
+int cgmres_hip_plant_info(int32_t model_id, int32_t* n_theta, double* nominal, int32_t cap);
+/* One plant step on the stream: x_dev <- Phi(x_dev, u_dev), x_dev [batch][dim_x] in/out, u_dev [batch][dim_u]; no d, no v.
+ * Changes no controller state; p (user models) is stage 0 of the handle's ptau.  CGMRES_HIP_EINVAL: what
+ * ..._closed_loop_device_plant refuses of a plant, a NULL plant, x_dev or u_dev.  Asynchronous on the handle's stream. */
+int cgmres_hip_plant_step_device(cgmres_hip_handle h, void* x_dev, const void* u_dev, const cgmres_hip_loop_plant* plant);
+/* cgmres_hip_closed_loop_device_rec against this plant; `in` and `rec` as there.  For tick k = 0 .. n_ticks-1
+ *     y_k     = x_k + v_k
+ *     u_k     = control(y_k)              with ptau_k
+ *     x_{k+1} = Phi(x_k, u_k) + d_k
+ * x_dev always holds the TRUE state (y lives in a buffer of the handle); a record sees the true x_{k+1}.  After the call
+ * the handle's time, U, dUdt, status and last ptau are as after ..._rec.  plant == NULL: exactly ..._rec.
+ * CGMRES_HIP_EINVAL, each with its own text: everything ..._rec refuses; a struct_size other than
+ * sizeof(cgmres_hip_loop_plant), a non-zero reserved, an unknown integrator, substeps outside 1 .. 4096, a
+ * theta_per_instance outside {0, 1}, theta_dev on a model with n_theta == 0, theta_dev overlapping x_dev, u_dev, a log or
+ * a sequence; a user model whose plugin was built before this entry point existed (rebuild the plugin).
+ * Asynchronous on the handle's stream. */
+int cgmres_hip_closed_loop_device_plant(cgmres_hip_handle h, void* x_dev, void* u_dev, int32_t n_ticks,
+                                        const cgmres_hip_loop_inputs* in, const cgmres_hip_loop_record* rec,
+                                        const cgmres_hip_loop_plant* plant);
 int cgmres_hip_synchronize(cgmres_hip_handle h);
 
 /* ---- state: the private members of Cgmres (cgmres.hpp:195-202) and Gmres (gmres.hpp:120-124) ------ */

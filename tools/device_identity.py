@@ -122,7 +122,12 @@ def main():
     doc = [f"Parent: commit {commit}.  `{' '.join(build.CFLAGS)}` plus `--cuda-device-only -S`.", "", "```"] + version + \
           ["```", "", "| translation unit | lines | sha256, parent | sha256, this change | |", "|---|---|---|---|---|"]
     notes, bad = [], 0
-    for (label, la), (_, lb) in zip(old, new):
+    parent_units = dict(old)
+    for label, lb in new:  # (by label: a unit this change adds has no parent)
+        if label not in parent_units:
+            doc.append(f"| {label} | {len(lb)} | — | `{sha(lb)}` | new in this change |")
+            continue
+        la = parent_units[label]
         cls, detail = classify(la, lb)
         word = {"identical": "identical", "commutative": "identical up to commutative source order",
                 "different": "DIFFERENT"}[cls]
