@@ -115,6 +115,11 @@ def test_device_gmres_with_a_user_operator_vs_the_reference(name):
         assert np.all((why == cg.EXIT_NATURAL) | (why == cg.EXIT_CONVERGED) | (why == cg.EXIT_BREAKDOWN))
         if tol > 0 and kmax >= L:
             assert np.all(why != cg.EXIT_NATURAL)   # a full Krylov space: converged (or broke down on the exact solve) before k_max
+        # ... and exactly: the counts and exit codes of the numpy reference (tests/gmres_numpy_ref.py; every one of them
+        # is decided: tests/test_gpu_user_gmres_exits.py)
+        import gmres_numpy_ref as gr  # (imports this module)
+        _, k_ref, why_ref, _ = gr.case_ref(name, c)
+        assert np.array_equal(n_ax, k_ref) and np.array_equal(why, why_ref), (name, kmax, tol, n_ax, k_ref, why, why_ref)
     # a second call with a different batch size reuses nothing (stateless) and a zero right-hand side leaves at the
     # residual test with x untouched (gmres.hpp:39-41)
     x0 = np.zeros((3, L))

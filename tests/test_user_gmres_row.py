@@ -236,6 +236,10 @@ def test_row_operator_vs_the_reference(name):
         assert np.all((why == cg.EXIT_NATURAL) | (why == cg.EXIT_CONVERGED) | (why == cg.EXIT_BREAKDOWN))
         if tol > 0 and kmax >= L:
             assert np.all(why != cg.EXIT_NATURAL)
+        # ... and exactly: the counts and exit codes of the numpy reference (tests/gmres_numpy_ref.py)
+        import gmres_numpy_ref as gr
+        _, k_ref, why_ref, _ = gr.case_ref(name, c)
+        assert np.array_equal(n_ax, k_ref) and np.array_equal(why, why_ref), (name, kmax, tol, n_ax, k_ref, why, why_ref)
 
 
 @pytest.mark.gpu
