@@ -41,9 +41,12 @@ SYMBOLS = [
     "cgmres_hip_memcpy_h2d", "cgmres_hip_memcpy_d2h", "cgmres_hip_state_rows", "cgmres_hip_horizon_device",
     "cgmres_hip_ensemble_device", "cgmres_hip_closed_loop_device_rec", "cgmres_hip_record_plan",
     "cgmres_hip_plant_info", "cgmres_hip_plant_step_device", "cgmres_hip_closed_loop_device_plant",
+    "cgmres_hip_closed_loop_device_preview", "cgmres_hip_preview_device",
 ]
 PLANT_EULER, PLANT_RK4 = 0, 1  # CGMRES_HIP_PLANT_*
 PLANT_INTEGRATORS = {"euler": PLANT_EULER, "rk4": PLANT_RK4}
+PREVIEW_HOLD, PREVIEW_LINEAR = 0, 1  # CGMRES_HIP_PREVIEW_*
+PREVIEW_INTERPS = {"hold": PREVIEW_HOLD, "linear": PREVIEW_LINEAR}
 
 
 class Config(C.Structure):
@@ -95,6 +98,49 @@ class Plant:
 
     def __init__(self, integrator="rk4", substeps=4, theta=None, theta_per_instance=None):
         self.integrator, self.substeps, self.theta, self.theta_per_instance = integrator, int(substeps), theta, theta_per_instance
+
+
+class LoopPreview(C.Structure):
+    """struct cgmres_hip_loop_preview (include/cgmres_hip.h): the sampled signal of cgmres_hip_closed_loop_device_preview."""
+    _fields_ = [("struct_size", C.c_int32), ("interp", C.c_int32), ("sig_per_instance", C.c_int32), ("n_samples", C.c_int32),
+                ("t0", C.c_double), ("ts", C.c_double), ("sig_dev", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
+class Preview:
+    """A sampled reference signal the device loop previews into every tick's ptau: sig is a device buffer
+    [batch, n_samples, dim_p] or one signal [n_samples, dim_p] for every instance, sample j taken at t0 + j*ts;
+    interp "linear" | "hold"; before t0 the first sample holds, past the end the last.  per_instance: for a raw address,
+    whose shape cannot be seen (then n_samples must be given too); otherwise decided by the buffer's shape."""
+
+    def __init__(self, sig, ts, t0=0.0, interp="linear", per_instance=None, n_samples=None):
+        self.sig, self.ts, self.t0, self.interp, self.per_instance, self.n_samples = sig, float(ts), float(t0), interp, per_instance, n_samples
+
+
+def preview_rows(sig, ts, t0, interp, t, dtau, dv):
+    """The rows a loop with a preview forms, restated in numpy (no GPU): for tick times t [n] and their dtau [n] (the
+    handle's own values), ptau rows [n, batch, (dv+1)*dim_p] (sig [batch, n_samples, dim_p]) or [n, (dv+1)*dim_p]
+    (sig [n_samples, dim_p]) in sig's dtype.  In double, statement for statement:
+        tau = t_k + i*dtau_k;  s = clamp((tau - t0)/ts, 0, n_samples-1)
+        hold:   j = min(floor(s), n_samples-1);          p = sig[j]
+        linear: j = min(floor(s), max(n_samples-2, 0));  p = sig[j] + (s - j)*(sig[j+1] - sig[j])   (one sample: sig[0])"""
+    sig = np.asarray(sig)
+    bcast = sig.ndim == 2
+    sg = (sig[None] if bcast else sig).astype(np.float64)
+    ns, dim_p = sg.shape[1], sg.shape[2]
+    t = np.atleast_1d(np.asarray(t)).astype(np.float64)
+    dtau = np.atleast_1d(np.asarray(dtau)).astype(np.float64)
+    tau = t[:, None] + np.arange(dv + 1, dtype=np.float64)[None, :] * dtau[:, None]  # [n, dv+1]
+    s = np.minimum(np.maximum((tau - float(t0)) / float(ts), 0.0), float(ns - 1))
+    linear = PREVIEW_INTERPS.get(interp, interp) == PREVIEW_LINEAR
+    if linear and ns > 1:
+        jf = np.minimum(np.floor(s), float(ns - 2))
+        j = jf.astype(np.int64)
+        lo, hi = sg[:, j, :], sg[:, j + 1, :]  # [batch, n, dv+1, dim_p]
+        p = lo + (s - jf)[None, :, :, None] * (hi - lo)
+    else:
+        p = sg[:, np.floor(s).astype(np.int64), :]
+    rows = np.transpose(p, (1, 0, 2, 3)).reshape(len(t), sg.shape[0], (dv + 1) * dim_p).astype(sig.dtype)
+    return rows[:, 0] if bcast else rows
 
 
 class CgmresHipError(RuntimeError):
@@ -172,6 +218,10 @@ def load():
         lib.cgmres_hip_plant_step_device.argtypes = [vp, vp, vp, C.POINTER(LoopPlant)]
         lib.cgmres_hip_closed_loop_device_plant.argtypes = [vp, vp, vp, i32, C.POINTER(LoopInputs), C.POINTER(LoopRecord),
                                                             C.POINTER(LoopPlant)]
+    if hasattr(lib, "cgmres_hip_closed_loop_device_preview"):  # (absent from A/B builds of older sources, tools/ab_build.py)
+        lib.cgmres_hip_closed_loop_device_preview.argtypes = [vp, vp, vp, i32, C.POINTER(LoopInputs), C.POINTER(LoopRecord),
+                                                              C.POINTER(LoopPlant), C.POINTER(LoopPreview)]
+        lib.cgmres_hip_preview_device.argtypes = [vp, C.POINTER(LoopPreview), i32, vp]
     if hasattr(lib, "cgmres_hip_state_rows"):  # (absent from A/B builds of older sources, tools/ab_build.py)
         lib.cgmres_hip_state_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
     _lib = lib
@@ -473,7 +523,8 @@ class CgmresBatch:
         return li
 
     def closed_loop_device(self, x_dev, u_dev, n_ticks, ptau_seq_dev=None, per_instance=True, *, dist_seq_dev=None,
-                           meas_seq_dev=None, dist_per_instance=True, meas_per_instance=True, record=None, plant=None):
+                           meas_seq_dev=None, dist_per_instance=True, meas_per_instance=True, record=None, plant=None,
+                           preview=None):
         """n_ticks of the example main loop on the device.  ptau_seq_dev: optional device array of per-tick parameter
         horizons, [n_ticks, batch, dim_p*(dv+1)] (per_instance) or [n_ticks, dim_p*(dv+1)] — `set_ptau` before every tick.
         dist_seq_dev / meas_seq_dev: optional device arrays [n_ticks, batch, dim_x] (or [n_ticks, dim_x], broadcast) of a
@@ -482,9 +533,21 @@ class CgmresBatch:
         record: a dict(stride=1, x=, u=, n_ax=, reason=, t=, centre=, moments=, counts=) of device buffers (t: a host float64
         array), every one optional — every stride-th tick is recorded into them (cgmres_hip_closed_loop_device_rec).
         plant: a Plant — x_{k+1} = Phi(x_k, u_k) + d_k with its integrator, substeps and parameters instead of the model's
-        Euler step, one tick per launch (cgmres_hip_closed_loop_device_plant)."""
+        Euler step, one tick per launch (cgmres_hip_closed_loop_device_plant).
+        preview: a Preview — every tick's ptau is formed on the device from its sampled signal and the handle's own t and
+        dtau, instead of ptau_seq_dev (cgmres_hip_closed_loop_device_preview)."""
         xp = _ptr(x_dev, self.np_dtype, self.batch * self.dim_x)
         up = _ptr(u_dev, self.np_dtype, self.batch * self.dim_u)
+        if preview is not None:
+            li = self._loop_inputs(n_ticks, ptau_seq_dev, per_instance, dist_seq_dev, meas_seq_dev, dist_per_instance,
+                                   meas_per_instance)
+            lr = self._loop_record(n_ticks, **record) if record is not None else None
+            lp = self._loop_plant(plant) if plant is not None else None
+            lv = self._loop_preview(preview)
+            _check(load().cgmres_hip_closed_loop_device_preview(self._h, xp, up, int(n_ticks), C.byref(li),
+                                                                C.byref(lr) if lr is not None else None,
+                                                                C.byref(lp) if lp is not None else None, C.byref(lv)))
+            return
         if ptau_seq_dev is not None and self.dim_p == 0:
             ptau_seq_dev = None
         if plant is not None:
@@ -512,6 +575,36 @@ class CgmresBatch:
         li = self._loop_inputs(n_ticks, ptau_seq_dev, per_instance, dist_seq_dev, meas_seq_dev, dist_per_instance,
                                meas_per_instance)
         _check(load().cgmres_hip_closed_loop_device_ex(self._h, xp, up, int(n_ticks), C.byref(li)))
+
+    # -- the preview of a sampled reference signal -------------------------------------------------------
+    def _loop_preview(self, preview):
+        """struct cgmres_hip_loop_preview of a Preview; a typed sig buffer is checked for element type and count (one signal
+        or one per instance, decided by its shape) before its address crosses the ABI."""
+        interp = preview.interp
+        lv = LoopPreview(struct_size=C.sizeof(LoopPreview), t0=preview.t0, ts=preview.ts,
+                         interp=PREVIEW_INTERPS[interp] if isinstance(interp, str) else int(interp))
+        sg, dim_p = preview.sig, self.dim_p
+        shape = tuple(sg.shape) if hasattr(sg, "shape") else None
+        if shape is not None:
+            if len(shape) not in (2, 3) or (dim_p and shape[-1] != dim_p) or (len(shape) == 3 and shape[0] != self.batch):
+                raise ValueError(f"preview sig must be [n_samples, {dim_p}] or [{self.batch}, n_samples, {dim_p}], got {shape}")
+            per, n_samples = len(shape) == 3, shape[-2]
+            if preview.per_instance is not None and bool(preview.per_instance) != per:
+                raise ValueError(f"preview per_instance={preview.per_instance} contradicts the signal's shape {shape}")
+        else:
+            if sg is not None and (preview.per_instance is None or preview.n_samples is None):
+                raise ValueError("a raw sig address needs per_instance and n_samples")
+            per, n_samples = bool(preview.per_instance), preview.n_samples if preview.n_samples is not None else 1
+        lv.sig_per_instance, lv.n_samples = 1 if per else 0, int(n_samples)
+        lv.sig_dev = _ptr(sg, self.np_dtype, None if shape is None else int(np.prod(shape)))
+        return lv
+
+    def preview_device(self, preview, n_ticks, rows):
+        """The rows a loop with this Preview would use for its next n_ticks ticks from the handle's current time, into the
+        device buffer rows [n_ticks, batch, dim_p*(dv+1)]; on the stream, changes no state (cgmres_hip_preview_device)."""
+        lv = self._loop_preview(preview)
+        n = int(n_ticks) * self.batch * self.dim_p * (self.dv + 1) if int(n_ticks) >= 0 else None
+        _check(load().cgmres_hip_preview_device(self._h, C.byref(lv), int(n_ticks), _ptr(rows, self.np_dtype, n)))
 
     # -- a plant of its own ----------------------------------------------------------------------------
     def _loop_plant(self, plant):
@@ -571,12 +664,13 @@ class CgmresBatch:
                                                  _ptr(u_dev, self.np_dtype, self.batch * self.dim_u), C.byref(out)))
 
     def closed_loop_record(self, x, n_ticks, stride=1, centre=None, u=None, ptau_seq=None, per_instance=True, dist_seq=None,
-                           meas_seq=None, dist_per_instance=True, meas_per_instance=True, plant=None):
+                           meas_seq=None, dist_per_instance=True, meas_per_instance=True, plant=None, preview=None):
         """The convenience form: n_ticks of the device loop from the host state x [batch, dim_x], every stride-th tick
         recorded; the sequences are host arrays.  Allocates, runs, synchronises and returns numpy arrays:
         dict(t [n_rec], x [n_rec, batch, dim_x], u [n_rec, batch, dim_u], n_ax, reason [n_rec, batch],
         moments [n_rec, dim_x+dim_u, 4], counts [n_rec, k_max+7], x_end, u_end).  plant: a Plant whose theta, if any, is a HOST
-        array [batch, n_theta] or [n_theta]."""
+        array [batch, n_theta] or [n_theta]; preview: a Preview whose sig may be a HOST
+        array [batch, n_samples, dim_p] or [n_samples, dim_p]."""
         n_ticks, stride = int(n_ticks), int(stride)
         n_rec, nc, B = n_ticks // stride, self.dim_x + self.dim_u, self.batch
         bufs = []
@@ -602,11 +696,14 @@ class CgmresBatch:
             if plant is not None and plant.theta is not None and isinstance(plant.theta, (np.ndarray, list, tuple)):
                 th = np.asarray(plant.theta, dtype=self.np_dtype)
                 plant = Plant(plant.integrator, plant.substeps, dev(th.shape, init=th), plant.theta_per_instance)
+            if preview is not None and isinstance(preview.sig, (np.ndarray, list, tuple)):
+                sg = np.asarray(preview.sig, dtype=self.np_dtype)
+                preview = Preview(dev(sg.shape, init=sg), preview.ts, preview.t0, preview.interp, preview.per_instance)
             self.closed_loop_device(xd, ud, n_ticks, seq(ptau_seq, per_instance, self.dim_p * (self.dv + 1)) if self.dim_p else None,
                                     per_instance, dist_seq_dev=seq(dist_seq, dist_per_instance, self.dim_x),
                                     meas_seq_dev=seq(meas_seq, meas_per_instance, self.dim_x),
                                     dist_per_instance=dist_per_instance, meas_per_instance=meas_per_instance, record=rec,
-                                    plant=plant)
+                                    plant=plant, preview=preview)
             out = {k: rec[k].download() for k in ("x", "u", "n_ax", "reason", "moments", "counts")}  # (blocks on the stream)
             out.update(t=t, x_end=xd.download(), u_end=ud.download())
             return out

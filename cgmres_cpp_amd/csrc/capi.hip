@@ -34,6 +34,7 @@ struct Plugin {
   cgm::HorizonFn* horizon;  // optional symbol: null in a plugin built before cgmres_hip_horizon_device existed
   int32_t (*record)(void);  // optional symbol: null in a plugin whose contexts predate the record kernels (status_dev)
   cgm::PlantFn* plant;      // optional symbol: null in a plugin built before cgmres_hip_closed_loop_device_plant existed
+  int32_t (*preview)(void);  // optional symbol: null in a plugin whose contexts' closed loops predate LoopSeqs::preview_fill
 };
 std::deque<Plugin>& plugins() {  // deque: find_plugin hands out pointers that must survive later push_backs
   static std::deque<Plugin> v;
@@ -299,6 +300,33 @@ int plant_rc(cgmres_hip_handle h, int rc) {
   return rc;
 }
 
+// A cgmres_hip_loop_preview, checked; on success *out describes the signal.  A plugin built before LoopSeqs carried a preview
+// reads only the struct's old prefix and would run without it: told to rebuild.
+int preview_check(cgmres_hip_handle h, const char* who, const cgmres_hip_loop_preview* pv, cgm::PreviewSig* out) {
+  if (pv->struct_size != int32_t(sizeof(cgmres_hip_loop_preview)))
+    return fail(CGMRES_HIP_EINVAL, "%s: struct_size %d, this library's cgmres_hip_loop_preview has %d", who, pv->struct_size,
+                int(sizeof(cgmres_hip_loop_preview)));
+  if (pv->reserved[0] != 0 || pv->reserved[1] != 0)
+    return fail(CGMRES_HIP_EINVAL, "%s: cgmres_hip_loop_preview.reserved must be 0 (got %d, %d)", who, pv->reserved[0], pv->reserved[1]);
+  if (pv->interp != CGMRES_HIP_PREVIEW_HOLD && pv->interp != CGMRES_HIP_PREVIEW_LINEAR)
+    return fail(CGMRES_HIP_EINVAL, "%s: unknown interp %d (CGMRES_HIP_PREVIEW_HOLD = 0, CGMRES_HIP_PREVIEW_LINEAR = 1)", who, pv->interp);
+  if (pv->sig_per_instance != 0 && pv->sig_per_instance != 1)
+    return fail(CGMRES_HIP_EINVAL, "%s: sig_per_instance is %d, not 0 or 1", who, pv->sig_per_instance);
+  if (pv->n_samples < 1) return fail(CGMRES_HIP_EINVAL, "%s: n_samples %d < 1", who, pv->n_samples);
+  if (!std::isfinite(pv->ts) || !(pv->ts > 0)) return fail(CGMRES_HIP_EINVAL, "%s: ts must be finite and > 0 (got %g)", who, pv->ts);
+  if (!std::isfinite(pv->t0)) return fail(CGMRES_HIP_EINVAL, "%s: t0 must be finite (got %g)", who, pv->t0);
+  if (h->np > 0 && !pv->sig_dev) return fail(CGMRES_HIP_EINVAL, "%s: null sig_dev on a model with dim_p = %d", who, h->np);
+  const Plugin* pl = find_plugin(h->cfg.model_id);
+  if (pl && !pl->preview)
+    return fail(CGMRES_HIP_EINVAL, "%s: the plugin %s was built before this entry point existed: rebuild it", who, pl->path.c_str());
+  out->sig = pv->sig_dev, out->per_instance = pv->sig_per_instance, out->n_samples = pv->n_samples, out->interp = pv->interp;
+  out->t0 = pv->t0, out->ts = pv->ts;
+  return 0;
+}
+size_t preview_sig_bytes(cgmres_hip_handle h, const cgmres_hip_loop_preview* pv) {
+  return size_t(pv->sig_per_instance ? h->cfg.batch : 1) * size_t(pv->n_samples) * h->np * (h->cfg.dtype == CGMRES_HIP_F32 ? 4 : 8);
+}
+
 __global__ void sincos_selftest_kernel(const double* a, double* s, double* c, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) cgm::sincos_f64(a[i], &s[i], &c[i]);
@@ -409,7 +437,8 @@ int cgmres_hip_register_model(const char* plugin_path, int32_t* model_id) {
   const int rc = open_plugin(
       plugins(), "model", "cgmres_hip_plugin_", plugin_path, model_id ? &n : nullptr, pl,
       {{"info", &info, true}, {"make", &pl.make, true}, {"probe", &pl.probe, true}, {"last_error", &pl.last_error, true},
-       {"horizon", &pl.horizon, false}, {"record", &pl.record, false}, {"plant", &pl.plant, false}},
+       {"horizon", &pl.horizon, false}, {"record", &pl.record, false}, {"plant", &pl.plant, false},
+       {"preview", &pl.preview, false}},
       [&](Plugin& q) {
         int32_t dims[5];
         double tun[6];
@@ -605,10 +634,15 @@ int cgmres_hip_ensemble_device(cgmres_hip_handle h, const void* x, const void* u
 }
 int cgmres_hip_closed_loop_device_rec(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const cgmres_hip_loop_inputs* in,
                                       const cgmres_hip_loop_record* rec) {
-  return cgmres_hip_closed_loop_device_plant(h, x, u, n_ticks, in, rec, nullptr);
+  return cgmres_hip_closed_loop_device_preview(h, x, u, n_ticks, in, rec, nullptr, nullptr);
 }
 int cgmres_hip_closed_loop_device_plant(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const cgmres_hip_loop_inputs* in,
                                         const cgmres_hip_loop_record* rec, const cgmres_hip_loop_plant* plant) {
+  return cgmres_hip_closed_loop_device_preview(h, x, u, n_ticks, in, rec, plant, nullptr);
+}
+int cgmres_hip_closed_loop_device_preview(cgmres_hip_handle h, void* x, void* u, int32_t n_ticks, const cgmres_hip_loop_inputs* in,
+                                          const cgmres_hip_loop_record* rec, const cgmres_hip_loop_plant* plant,
+                                          const cgmres_hip_loop_preview* preview) {
   NEED(h);
   cgm::LoopSeqs sq;
   if (int rc = loop_seqs(h, x, u, n_ticks, in, &sq)) return rc;
@@ -634,6 +668,23 @@ int cgmres_hip_closed_loop_device_plant(cgmres_hip_handle h, void* x, void* u, i
       if (overlap(theta, o))
         return fail(CGMRES_HIP_EINVAL, "closed_loop_device_plant: theta_dev overlaps %s (cgmres.hpp DEBUG_MODE alias guard)", o.name);
   }
+  Range sig{"sig_dev", nullptr, 0};
+  if (preview) {
+    if (int rc = preview_check(h, "closed_loop_device_preview", preview, &sq.preview)) return rc;
+    if (in && in->ptau_seq_dev)
+      return fail(CGMRES_HIP_EINVAL, "closed_loop_device_preview: ptau_seq_dev and a preview are both given: the preview forms every tick's ptau");
+    sig = {"sig_dev", preview->sig_dev, preview_sig_bytes(h, preview)};
+    // the alias guard, extended: the signal shares no byte with x_dev, u_dev, an input sequence or theta (the logs: below)
+    const Range io[5] = {{"x_dev", x, B * h->nx * es},
+                         {"u_dev", u, B * h->nu * es},
+                         {"dist_seq_dev", sq.dist, seq_rows * (sq.dist_per_instance ? B : 1) * h->nx * es},
+                         {"meas_seq_dev", sq.meas, seq_rows * (sq.meas_per_instance ? B : 1) * h->nx * es},
+                         theta};
+    for (const Range& o : io)
+      if (overlap(sig, o))
+        return fail(CGMRES_HIP_EINVAL, "closed_loop_device_preview: sig_dev overlaps %s (cgmres.hpp DEBUG_MODE alias guard)", o.name);
+    if (h->np > 0) sq.preview_fill = cgm::preview_fill;  // (dim_p = 0: ignored, as a ptau sequence is)
+  }
   auto run = [&] { return plant ? plant_rc(h, closed_loop(h, x, u, n_ticks, sq)) : closed_loop(h, x, u, n_ticks, sq); };
   if (!rec) return run();
   if (rec->struct_size != int32_t(sizeof(cgmres_hip_loop_record)))
@@ -653,13 +704,14 @@ int cgmres_hip_closed_loop_device_plant(cgmres_hip_handle h, void* x, void* u, i
   const Range logs[6] = {{"x_log_dev", rec->x_log_dev, n_rec * B * h->nx * es},       {"u_log_dev", rec->u_log_dev, n_rec * B * h->nu * es},
                          {"n_ax_log_dev", rec->n_ax_log_dev, n_rec * B * 4},          {"reason_log_dev", rec->reason_log_dev, n_rec * B * 4},
                          {"moments_log_dev", rec->moments_log_dev, n_rec * nc * 32}, {"counts_log_dev", rec->counts_log_dev, n_rec * size_t(h->cfg.k_max + 7) * 4}};
-  const Range others[7] = {{"x_dev", x, B * h->nx * es},
+  const Range others[8] = {{"x_dev", x, B * h->nx * es},
                            {"u_dev", u, B * h->nu * es},
                            {"ptau_seq_dev", sq.ptau, seq_rows * (sq.ptau_per_instance ? B : 1) * h->np * (h->cfg.dv + 1) * es},
                            {"dist_seq_dev", sq.dist, seq_rows * (sq.dist_per_instance ? B : 1) * h->nx * es},
                            {"meas_seq_dev", sq.meas, seq_rows * (sq.meas_per_instance ? B : 1) * h->nx * es},
                            {"centre_dev", rec->centre_dev, nc * 8},
-                           theta};
+                           theta,
+                           sig};
   for (int i = 0; i < 6; ++i) {
     for (const Range& o : others)
       if (overlap(logs[i], o)) return fail(CGMRES_HIP_EINVAL, "closed_loop_device_rec: %s overlaps %s (cgmres.hpp DEBUG_MODE alias guard)", logs[i].name, o.name);
@@ -700,6 +752,21 @@ int cgmres_hip_plant_step_device(cgmres_hip_handle h, void* x, const void* u, co
   c.x = x, c.u = u, c.theta = sq.plant_theta, c.theta_inst = sq.plant_theta_inst;
   c.integrator = sq.plant_integrator, c.substeps = sq.plant_substeps;
   return plant_rc(h, sq.plant_step(h, c));
+}
+int cgmres_hip_preview_device(cgmres_hip_handle h, const cgmres_hip_loop_preview* preview, int32_t n_ticks, void* rows) {
+  NEED(h);
+  if (!preview) return fail(CGMRES_HIP_EINVAL, "preview_device: null preview");
+  if (!rows) return fail(CGMRES_HIP_EINVAL, "preview_device: null rows_dev");
+  if (n_ticks < 0) return fail(CGMRES_HIP_EINVAL, "preview_device: n_ticks < 0");
+  cgm::PreviewSig s;
+  if (int rc = preview_check(h, "preview_device", preview, &s)) return rc;
+  const size_t es = h->cfg.dtype == CGMRES_HIP_F32 ? 4 : 8, sb = preview_sig_bytes(h, preview);
+  const size_t rb = size_t(n_ticks) * h->cfg.batch * h->np * (h->cfg.dv + 1) * es;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(preview->sig_dev), b = reinterpret_cast<uintptr_t>(rows);
+  if (sb && rb && a < b + rb && b < a + sb)
+    return fail(CGMRES_HIP_EINVAL, "preview_device: sig_dev overlaps rows_dev (cgmres.hpp DEBUG_MODE alias guard)");
+  ENTER(h);
+  return cgm::preview_export(h, s, n_ticks, rows);
 }
 int cgmres_hip_horizon_device(cgmres_hip_handle h, const void* x, const cgmres_hip_horizon_out* out) {
   NEED(h);

@@ -57,6 +57,20 @@ struct PlantCall {
   int integrator = 0;    // CGMRES_HIP_PLANT_*
   int substeps = 1;      // 0: measure only (y = x + v, x untouched)
 };
+// The sampled reference signal of a loop with a preview (cgmres_hip_loop_preview, validated by capi.hip) and one launch of
+// preview_kernel (preview.hip.h) on a context's stream: rows [n][batch][dim_p*(dv+1)] of the n <= CGMRES_HIP_TICKS_PER_LAUNCH
+// ticks whose (t_k, dtau_k) the host array tab [2n] holds, in the handle's dtype.
+struct PreviewSig {
+  const void* sig = nullptr;  // [batch or 1][n_samples][dim_p], handle dtype
+  int per_instance = 0, n_samples = 0, interp = 0;
+  double t0 = 0, ts = 1;
+};
+struct PreviewCall {
+  const PreviewSig* s = nullptr;
+  void* rows = nullptr;
+  int n = 0;
+  const void* tab = nullptr;
+};
 // Per-tick input sequences of the closed loop (cgmres_hip_loop_inputs, validated by capi.hip): device pointers,
 // [n_ticks][batch or 1][...]; null = absent
 struct LoopSeqs {
@@ -81,7 +95,25 @@ struct LoopSeqs {
   int plant_integrator = 0, plant_substeps = 1;
   const void* plant_theta = nullptr;
   int plant_theta_inst = 0;
+  // The preview of cgmres_hip_closed_loop_device_preview (preview.hip.h): null preview_fill = none.  A context that is given
+  // one fills, in front of every launch of its cut, the rows of that launch's ticks in a ring it owns and points the tick
+  // kernel's ptau sequence at them.  A pointer like rec_take: the function lives in the library, whatever made the context.
+  int (*preview_fill)(cgmres_hip_ctx* c, const PreviewCall& call) = nullptr;
+  PreviewSig preview;
 };
+// The clock of a handle in its dtype T, stated once: dtau(t) (cgmres.hpp:32-34) and, in tick_clock, the (t_k, dtau_k) of
+// the n ticks from t on as control() advances it (t += dt, cgmres.hpp:107).  Evaluated on the host for the whole batch.
+template <class T>
+inline T dtau_of(const cgmres_hip_config& cfg, T tt) {
+  return T(cfg.Tf) * (1 - std::exp(-T(cfg.alpha) * tt)) / T(cfg.dv);
+}
+template <class T>
+inline void tick_clock(const cgmres_hip_config& cfg, T t, int n, T* tab) {
+  for (int k = 0; k < n; ++k) {
+    tab[2 * k] = t, tab[2 * k + 1] = dtau_of(cfg, t);
+    t = t + T(cfg.dt);
+  }
+}
 }  // namespace cgm
 
 // Type-erased controller batch: what a cgmres_hip_handle points to.

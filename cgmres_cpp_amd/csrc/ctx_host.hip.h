@@ -32,7 +32,7 @@ struct CtxHost : cgmres_hip_ctx {
   D& self() { return static_cast<D&>(*this); }
 
   T dtau_of(T tt) const {  // cgmres.hpp:32-34, evaluated once per tick on the host for the whole batch
-    return T(cfg.Tf) * (1 - std::exp(-T(cfg.alpha) * tt)) / T(cfg.dv);
+    return cgm::dtau_of<T>(cfg, tt);
   }
   double time() const override { return double(t); }
 
@@ -138,6 +138,18 @@ struct CtxHost : cgmres_hip_ctx {
     if (k >= 0 && dseq) c.d = dseq + size_t(k) * d_tick, c.d_inst = sq.dist_per_instance ? nx : 0;
     if (mseq && k + 1 < n_ticks) c.v = mseq + size_t(k + 1) * m_tick, c.v_inst = sq.meas_per_instance ? nx : 0, c.y = plant_y;
     return sq.plant_step(this, c);
+  }
+  // The rows of a loop with a preview (LoopSeqs::preview_fill): a ring of the mapping's ticks per launch, grown on demand,
+  // rewritten in front of every launch on the stream (so behind the launch that read it last) and freed with the handle.
+  T* pv_ring = nullptr;  // [ticks per launch][B][np * (dv+1)], caller layout
+  size_t pv_ring_n = 0;
+  // fills the ring's first n rows for the n ticks from the handle's time on
+  int preview_rows(const LoopSeqs& sq, int n) {
+    T tab[2 * CGMRES_HIP_TICKS_PER_LAUNCH];
+    tick_clock<T>(cfg, t, n, tab);
+    PreviewCall c;
+    c.s = &sq.preview, c.rows = pv_ring, c.n = n, c.tab = tab;
+    return sq.preview_fill(this, c);
   }
 };
 

@@ -103,6 +103,11 @@ struct CtxLane final : CtxHost<M, T, CtxLane<M, T>> {
       if ((rc = grow(&this->plant_y, &this->plant_y_n, size_t(cfg.batch) * nx))) return rc;
       x_seen = Host::plant_y;
     }
+    // a loop with a preview (LoopSeqs::preview_fill): a ring of one row, filled in front of every tick and set as a row of
+    // a ptau sequence is
+    const bool pv = sq.preview_fill != nullptr && all && n_ticks > 0;
+    if (pv)
+      if ((rc = grow(&this->pv_ring, &this->pv_ring_n, size_t(cfg.batch) * all))) return rc;
     const HorizonView<const T> p0{P.ptau, 1, size_t(ldb)};  // (the handle's ptau holds this tick's horizon: set below)
     RecordCut cut(n_ticks, sq.rec_take ? sq.rec_stride : 0, 1);  // (one tick per launch: the cut only says where a record is due)
     while (!cut.done() && !rc) {
@@ -110,7 +115,12 @@ struct CtxLane final : CtxHost<M, T, CtxLane<M, T>> {
       bool rec = false;
       cut.next(&rec);
       const T t_tick = t;
-      if (sq.ptau && all) {  // set_ptau before this tick (cgmres.hpp:36-39), device to device
+      if (pv) {
+        if ((rc = Host::preview_rows(sq, 1))) break;
+        dim3 grid((cfg.batch + 255) / 256, all);
+        to_element_major<T><<<grid, 256, 0, stream>>>(P.ptau, Host::pv_ring, cfg.batch, ldb, all, 0);
+        HIP_TRY(hipGetLastError());
+      } else if (sq.ptau && all) {  // set_ptau before this tick (cgmres.hpp:36-39), device to device
         dim3 grid((cfg.batch + 255) / 256, all);
         to_element_major<T><<<grid, 256, 0, stream>>>(P.ptau, static_cast<const T*>(sq.ptau) + i * per_tick, cfg.batch,
                                                        ldb, all, !per_instance);

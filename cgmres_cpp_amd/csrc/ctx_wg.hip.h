@@ -212,9 +212,17 @@ struct CtxWg final : CtxHost<M, T, CtxWg<M, T>> {
     return 0;
   }
   int closed_loop(void* x, void* u, int n_ticks, const LoopSeqs& sq) override {
-    const int all = np * (cfg.dv + 1), per_instance = sq.ptau_per_instance;
-    const T* seq = all ? static_cast<const T*>(sq.ptau) : nullptr;
+    const int all = np * (cfg.dv + 1);
+    // a loop with a preview (LoopSeqs::preview_fill): the sequence is the ring of this context, one row per instance and
+    // tick of a launch, filled in front of every launch; row i of the loop is row i - (the launch's first tick) of the ring
+    const bool pv = sq.preview_fill != nullptr && all && n_ticks > 0;
+    const int per_instance = pv ? 1 : sq.ptau_per_instance;
     const size_t per_tick = size_t(per_instance ? cfg.batch : 1) * all;
+    if (pv)
+      if (int rc = grow(&this->pv_ring, &this->pv_ring_n, size_t(CGM_FUSE_MAX) * per_tick)) return rc;
+    const T* seq = pv ? Host::pv_ring : all ? static_cast<const T*>(sq.ptau) : nullptr;
+    int first = 0;  // the first tick of the launch the ring holds
+    auto row = [&](int i) { return seq + size_t(pv ? i - first : i) * per_tick; };
     P.pseq_tick = per_tick, P.pseq_inst = per_instance ? all : 0;
     // plant inputs (cgmres_hip_closed_loop_device_ex): d and v, [n_ticks][batch or 1][nx]
     PlantSeqs<T> ps{static_cast<const T*>(sq.dist), static_cast<const T*>(sq.meas),
@@ -231,7 +239,7 @@ struct CtxWg final : CtxHost<M, T, CtxWg<M, T>> {
     }
     // stage 0 of the horizon tick i is given: row i of the sequence, or the handle's ptau
     auto p_of = [&](int i) {
-      return seq ? HorizonView<const T>{seq + size_t(i) * per_tick, size_t(per_instance ? all : 0), 1}
+      return seq ? HorizonView<const T>{row(i), size_t(per_instance ? all : 0), 1}
                  : HorizonView<const T>{P.ptau, size_t(all), 1};
     };
     // (a lambda, so that a failed launch check leaves through the line below it, which takes the per-launch pointers off
@@ -245,7 +253,11 @@ struct CtxWg final : CtxHost<M, T, CtxWg<M, T>> {
         const int i = cut.i;
         bool rec = false;
         const int n = cut.next(&rec);
-        P.ptau_seq = seq ? seq + size_t(i) * per_tick : nullptr;  // the kernel reloads ptau at the top of every tick
+        if (pv) {
+          first = i;
+          if (int rv = Host::preview_rows(sq, n)) return rv;
+        }
+        P.ptau_seq = seq ? row(i) : nullptr;  // the kernel reloads ptau at the top of every tick
         if (plant_in) {  // this launch's rows, through the device-resident record the kernel reads (stream-ordered)
           PlantSeqs<T> q = ps;
           q.dist = ps.dist ? ps.dist + size_t(i) * ps.dist_tick : nullptr;
@@ -275,7 +287,7 @@ struct CtxWg final : CtxHost<M, T, CtxWg<M, T>> {
     const int rc = launches();
     P.ptau_seq = nullptr, P.pin = nullptr, P.perm = nullptr;  // control() and the hooks take none of them
     if (!rc && seq && n_ticks > 0) {  // the handle keeps the last tick's ptau, as set_ptau would (cgmres.hpp:36-39)
-      replicate_rows_im<T><<<dim3(4, cfg.batch), 256, 0, stream>>>(P.ptau, all, seq + size_t(n_ticks - 1) * per_tick,
+      replicate_rows_im<T><<<dim3(4, cfg.batch), 256, 0, stream>>>(P.ptau, all, row(n_ticks - 1),
                                                                     cfg.batch, all, 1, !per_instance);
       HIP_TRY(hipGetLastError());
     }

@@ -30,6 +30,11 @@ struct RecordOut {
   int32_t* counts;
 };
 int record_take(cgmres_hip_ctx* c, const void* x, const void* u, const int32_t* n_ax, const int32_t* reason, const RecordOut& o);
+// The preview of a sampled reference signal (preview.hip.h), on the context's stream: preview_fill = one launch of the
+// kernel (LoopSeqs::preview_fill), preview_export = rows [n_ticks][batch][dim_p*(dv+1)] from the handle's time on, without
+// touching it.  Independent of model and mapping like record_take: both in inst_preview.hip.
+int preview_fill(cgmres_hip_ctx* c, const PreviewCall& call);
+int preview_export(cgmres_hip_ctx* c, const PreviewSig& s, int n_ticks, void* rows);
 #ifdef CGM_STAMPS
 long long* debug_stamps_ptr();  // diagnostic build only: stamp buffer of the last pendulum/f64 wg context
 #endif

@@ -235,8 +235,19 @@ extern "C" int cgmres_hip_plugin_debug_lds_oob(void) {
   }
 #endif
 
-// The entry points of a model plugin (bound by cgmres_hip_register_model in capi.hip): four required, horizon, record and
-// plant optional.
+// The fourth optional entry point says that the closed loops of the plugin's contexts know LoopSeqs::preview_fill
+// (cgmres_hip_closed_loop_device_preview, cgmres_hip_preview_device): one built before reads only the old prefix of
+// LoopSeqs and would run without the preview.  The library refuses those two calls, and nothing else, for a plugin
+// without it, which the tests imitate with -DCGM_PLUGIN_WITHOUT_PREVIEW.
+#ifdef CGM_PLUGIN_WITHOUT_PREVIEW
+#define CGM_PLUGIN_PREVIEW
+#else
+#define CGM_PLUGIN_PREVIEW \
+  int32_t cgmres_hip_plugin_preview(void) { return 1; }
+#endif
+
+// The entry points of a model plugin (bound by cgmres_hip_register_model in capi.hip): four required, horizon, record,
+// plant and preview optional.
 #define CGMRES_HIP_DEFINE_PLUGIN(MODEL)                                                                          \
   extern "C" {                                                                                                   \
   int32_t cgmres_hip_plugin_abi(void) { return CGMRES_HIP_ABI_VERSION; }                                         \
@@ -273,4 +284,5 @@ extern "C" int cgmres_hip_plugin_debug_lds_oob(void) {
   CGM_PLUGIN_HORIZON(MODEL)                                                                                      \
   CGM_PLUGIN_RECORD                                                                                              \
   CGM_PLUGIN_PLANT(MODEL)                                                                                        \
+  CGM_PLUGIN_PREVIEW                                                                                             \
   }

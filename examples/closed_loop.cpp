@@ -10,6 +10,9 @@
 //   ... --device-loop --plant euler|rk4:N          the device loop against a plant of its own: N substeps of dt/N of forward
 //                                                  Euler or RK4 on the model's state equation, nominal parameters
 //                                                  (cgmres_hip_closed_loop_device_plant; euler:1 is the mains' plant)
+//   ... --device-loop --preview                    (pendulum, msd) the set point follows a slow sinusoid, sampled once per
+//                                                  tick; the device loop previews it into every tick's parameter horizon
+//                                                  (cgmres_hip_closed_loop_device_preview)
 //   closed_loop batch <B>  [ticks]                B perturbed pendulum controllers, dv=50, k_max=10, CgmresBatch
 //   closed_loop sharded <B> <dev,dev,...> [ticks]  the same batch owned shard by shard on the listed devices
 //                                                  (CgmresBatchSharded; a device may be listed twice), checked against
@@ -85,6 +88,7 @@ static const double kSemiX0[2] = {2.0, 0.0}, kSemiU0[3] = {0.028393761456740, 0.
 
 static bool g_device_loop = false;  // --device-loop
 static cgmres_hip_loop_plant g_plant = {};  // --plant euler|rk4:N (struct_size 0: none given)
+static bool g_preview = false;              // --preview
 template <class Model>
 static int run_single_device(const char* prefix, int ticks, const double* x0, const double* u0, const double* p);
 
@@ -110,7 +114,8 @@ template <class Model>
 struct DeviceLoop {
   CgmresBatch<Model> controller{1};
   std::vector<double> x, u, t;
-  double *x_dev = nullptr, *u_dev = nullptr, *x_log = nullptr, *u_log = nullptr;
+  double *x_dev = nullptr, *u_dev = nullptr, *x_log = nullptr, *u_log = nullptr, *sig_dev = nullptr;
+  int32_t n_samples = 0;
   std::string prefix;
   int ticks;
   DeviceLoop(const std::string& prefix_, int ticks_, const double* x0, const double* u0, const double* p)
@@ -129,15 +134,30 @@ struct DeviceLoop {
     for (int i = 0; i < 4; ++i) cgmres_detail::check(cgmres_hip_malloc(h, reinterpret_cast<void**>(bufs[i]), bytes[i]), "malloc");
     cgmres_detail::check(cgmres_hip_memcpy_h2d(h, x_dev, x.data(), bytes[0]), "memcpy_h2d");
     cgmres_detail::check(cgmres_hip_memcpy_h2d(h, u_dev, u.data(), bytes[1]), "memcpy_h2d");
+    if (g_preview && Model::dim_p > 0) {  // p(t) = p * (1 + 0.1 sin(2 pi t / 4 s)) in component 0, one sample per tick
+      n_samples = int32_t(n) + 1;
+      std::vector<double> sig(size_t(n_samples) * Model::dim_p);
+      for (int32_t j = 0; j < n_samples; ++j)
+        for (int c = 0; c < Model::dim_p; ++c)
+          sig[size_t(j) * Model::dim_p + c] = c == 0 ? p[c] * (1.0 + 0.1 * sin(2.0 * kPi * Model::dt * j / 4.0)) : p[c];
+      cgmres_detail::check(cgmres_hip_malloc(h, reinterpret_cast<void**>(&sig_dev), sizeof(double) * sig.size()), "malloc");
+      cgmres_detail::check(cgmres_hip_memcpy_h2d(h, sig_dev, sig.data(), sizeof(double) * sig.size()), "memcpy_h2d");
+    }
   }
   ~DeviceLoop() {
-    for (double* q : {x_dev, u_dev, x_log, u_log}) cgmres_hip_free(controller.native_handle(), q);
+    for (double* q : {x_dev, u_dev, x_log, u_log, sig_dev})
+      if (q) cgmres_hip_free(controller.native_handle(), q);
   }
   void enqueue() {
     cgmres_hip_loop_record rec = {};
     rec.struct_size = int32_t(sizeof rec), rec.stride = 1;
     rec.x_log_dev = x_log, rec.u_log_dev = u_log, rec.t_host = t.data();
-    if (g_plant.struct_size)
+    if (sig_dev) {
+      cgmres_hip_loop_preview pv = {};
+      pv.struct_size = int32_t(sizeof pv), pv.interp = CGMRES_HIP_PREVIEW_LINEAR, pv.n_samples = n_samples;
+      pv.t0 = 0.0, pv.ts = Model::dt, pv.sig_dev = sig_dev;
+      controller.closed_loop_device(x_dev, u_dev, ticks, nullptr, &rec, g_plant.struct_size ? &g_plant : nullptr, pv);
+    } else if (g_plant.struct_size)
       controller.closed_loop_device(x_dev, u_dev, ticks, nullptr, &rec, g_plant);
     else
       controller.closed_loop_device(x_dev, u_dev, ticks, nullptr, rec);
@@ -318,6 +338,10 @@ int main(int argc, char** argv) {
       g_device_loop = true;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc, --i;
+    } else if (!strcmp(argv[i], "--preview")) {
+      g_preview = true;
+      for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+      --argc, --i;
     } else if (!strcmp(argv[i], "--plant") && i + 1 < argc) {  // euler | rk4, optionally :N substeps
       const char* spec = argv[i + 1];
       const char* colon = strchr(spec, ':');
@@ -335,8 +359,8 @@ int main(int argc, char** argv) {
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2, --i;
     }
-  if (g_plant.struct_size && !g_device_loop) {
-    fprintf(stderr, "--plant needs --device-loop\n");
+  if ((g_plant.struct_size || g_preview) && !g_device_loop) {
+    fprintf(stderr, "--plant and --preview need --device-loop\n");
     return 1;
   }
   const char* which = argc > 1 ? argv[1] : "pendulum";
@@ -355,6 +379,6 @@ int main(int argc, char** argv) {
     return run_single<examples::SemiactiveModel<50, 5>, examples::SemiactivePlant>(
         prefix ? prefix : "semiactive_damper", ticks < 0 ? 20001 : ticks, kSemiX0, kSemiU0, kSemiX0 /*unused: dim_p = 0*/);
   if (!strcmp(which, "multiple")) return run_multiple(prefix ? prefix : "multiple_controller_", ticks < 0 ? 10001 : ticks);
-  fprintf(stderr, "usage: %s pendulum|msd|semiactive|multiple [ticks] [prefix] [--device-loop [--plant euler|rk4:N]]  |  batch <B> [ticks]  |  sharded <B> <dev,dev,..> [ticks]\n", argv[0]);
+  fprintf(stderr, "usage: %s pendulum|msd|semiactive|multiple [ticks] [prefix] [--device-loop [--plant euler|rk4:N] [--preview]]  |  batch <B> [ticks]  |  sharded <B> <dev,dev,..> [ticks]\n", argv[0]);
   return 2;
 }

@@ -85,6 +85,20 @@ class CgmresBatch {
                           const cgmres_hip_loop_record* rec, const cgmres_hip_loop_plant& plant) {
     cgmres_detail::check(cgmres_hip_closed_loop_device_plant(handle_, x_dev, u_dev, n_ticks, in, rec, &plant), "closed_loop_device_plant");
   }
+  // the same loop with a PREVIEW of a sampled reference signal: every tick's ptau is formed on the device from
+  // preview.sig_dev ([batch or 1][n_samples][dim_p], sample j at t0 + j*ts) and the controllers' own t and dtau, the ticks
+  // staying fused — cgmres_hip_closed_loop_device_preview.  `in`, `rec` and `plant` may be null; `preview.struct_size` must
+  // be sizeof(cgmres_hip_loop_preview)
+  void closed_loop_device(double* x_dev, double* u_dev, int32_t n_ticks, const cgmres_hip_loop_inputs* in,
+                          const cgmres_hip_loop_record* rec, const cgmres_hip_loop_plant* plant, const cgmres_hip_loop_preview& preview) {
+    cgmres_detail::check(cgmres_hip_closed_loop_device_preview(handle_, x_dev, u_dev, n_ticks, in, rec, plant, &preview),
+                         "closed_loop_device_preview");
+  }
+  // the rows that loop would use for its next n_ticks ticks, rows_dev [n_ticks][batch][dim_p*(dv+1)]: what a caller plots.
+  // Asynchronous on the handle's stream; changes no state
+  void preview_device(const cgmres_hip_loop_preview& preview, int32_t n_ticks, double* rows_dev) {
+    cgmres_detail::check(cgmres_hip_preview_device(handle_, &preview, n_ticks, rows_dev), "preview_device");
+  }
   // one step of that plant on the stream, x_dev <- Phi(x_dev, u_dev): no d, no v, no controller state changes
   void plant_step_device(double* x_dev, const double* u_dev, const cgmres_hip_loop_plant& plant) {
     cgmres_detail::check(cgmres_hip_plant_step_device(handle_, x_dev, u_dev, &plant), "plant_step_device");
@@ -126,6 +140,8 @@ class CgmresBatch {
 // cgmres_hip_loop_record, ensemble_device) are not offered here: an ensemble over shards needs a combine across devices;
 // shard(r) gives the per-shard calls.  Nor is the loop against a plant of its own (cgmres_hip_loop_plant,
 // plant_step_device): its theta_dev is a per-device array the caller would have to cut along the shards; shard(r) again.
+// Nor is the loop with a preview (cgmres_hip_loop_preview, preview_device): its sig_dev is a per-device array — instance-major,
+// so the slice of shard r is contiguous — that the caller uploads shard by shard; shard(r) once more.
 template <class Model>
 class CgmresBatchSharded {
  public:

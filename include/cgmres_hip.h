@@ -365,6 +365,52 @@ int cgmres_hip_plant_step_device(cgmres_hip_handle h, void* x_dev, const void* u
 int cgmres_hip_closed_loop_device_plant(cgmres_hip_handle h, void* x_dev, void* u_dev, int32_t n_ticks,
                                         const cgmres_hip_loop_inputs* in, const cgmres_hip_loop_record* rec,
                                         const cgmres_hip_loop_plant* plant);
+/* ---- a closed loop that previews a sampled reference signal ------------------------------------------------------------- */
+/* The parameter horizon of a controller is ptau = [ p(t), p(t + dtau), ..., p(t + dv*dtau) ] (cgmres.hpp:37) with
+ * dtau = get_dtau(t) (cgmres.hpp:32-34).  ptau_seq_dev takes it ready-made for every tick, [n_ticks][batch][dim_p*(dv+1)];
+ * here the caller hands over the SIGNAL p, sampled on a uniform grid, and the loop forms every tick's ptau on the device
+ * from the handle's own t and dtau, while the ticks stay fused.  sig_dev is a device array of the handle's dtype,
+ * [batch][n_samples][dim_p] (sig_per_instance = 1; instance-major, so a shard is a contiguous slice) or one signal
+ * [n_samples][dim_p] for every instance (0); sample j is p at time t0 + j*ts.  For the tick at the handle's time t_k, stage
+ * i = 0 .. dv and component c, in double for fp32 handles too:
+ *     tau = double(t_k) + i * double(dtau_k)                            dtau_k = get_dtau(t_k) in the handle's dtype
+ *     s   = clamp((tau - t0) / ts, 0, n_samples - 1)
+ *     CGMRES_HIP_PREVIEW_HOLD:    j = min(floor(s), n_samples-1);           p = sig[j][c]
+ *     CGMRES_HIP_PREVIEW_LINEAR:  j = min(floor(s), max(n_samples-2, 0));   p = sig[j][c] + (s - j)*(sig[j+1][c] - sig[j][c])
+ *                                                                           (n_samples == 1: p = sig[0][c])
+ *     ptau_k[i*dim_p + c] = p, rounded to the handle's dtype
+ * Before t0 the first sample holds, past the end the last.  The rows are written by a kernel of its own in front of every
+ * launch, into a ring of CGMRES_HIP_TICKS_PER_LAUNCH rows the handle owns (allocated on first use, freed with the handle),
+ * on the handle's stream. */
+enum { CGMRES_HIP_PREVIEW_HOLD = 0, CGMRES_HIP_PREVIEW_LINEAR = 1 };
+typedef struct cgmres_hip_loop_preview {
+  int32_t struct_size;      /* sizeof(cgmres_hip_loop_preview); anything else: CGMRES_HIP_EINVAL */
+  int32_t interp;           /* CGMRES_HIP_PREVIEW_* */
+  int32_t sig_per_instance; /* 0 / 1 */
+  int32_t n_samples;        /* >= 1 */
+  double t0;                /* the time of sample 0; finite */
+  double ts;                /* the sample period; finite, > 0 */
+  const void* sig_dev;      /* handle's dtype; may be NULL when dim_p = 0 */
+  int32_t reserved[2];      /* 0 */
+} cgmres_hip_loop_preview;
+/* cgmres_hip_closed_loop_device_plant with such a preview; `in`, `rec` and `plant` as there, each may be NULL.  Tick k runs
+ * with the ptau_k above; a record's cut decides the launch sizes as without a preview, a plant of its own runs one tick per
+ * launch and a user model's plant reads stage 0 of that tick's row.  After the call the handle keeps the last tick's row as
+ * its ptau, exactly as after a ptau_seq_dev loop, and the loop is, bit for bit, the ptau_seq_dev loop over the rows
+ * cgmres_hip_preview_device exports.  With dim_p = 0 the preview is ignored, as a ptau sequence is.  preview == NULL:
+ * exactly ..._plant.  CGMRES_HIP_EINVAL, each with its own text: everything ..._plant refuses; a struct_size other than
+ * sizeof(cgmres_hip_loop_preview), a non-zero reserved, interp or sig_per_instance outside its values, n_samples < 1, ts
+ * not finite or <= 0, t0 not finite, sig_dev NULL on a model with dim_p > 0, in->ptau_seq_dev together with a preview,
+ * sig_dev overlapping x_dev, u_dev, a log, a sequence or theta_dev; a user model whose plugin was built before this entry
+ * point existed (rebuild the plugin).  Asynchronous on the handle's stream. */
+int cgmres_hip_closed_loop_device_preview(cgmres_hip_handle h, void* x_dev, void* u_dev, int32_t n_ticks,
+                                          const cgmres_hip_loop_inputs* in, const cgmres_hip_loop_record* rec,
+                                          const cgmres_hip_loop_plant* plant, const cgmres_hip_loop_preview* preview);
+/* The rows that loop WOULD use for its next n_ticks ticks from the handle's current time: rows_dev
+ * [n_ticks][batch][dim_p*(dv+1)], handle's dtype.  What a caller plots.  Stream-ordered on the handle's stream and
+ * asynchronous; changes no state (not the time, not the handle's ptau).  dim_p = 0 or n_ticks = 0 writes nothing.
+ * CGMRES_HIP_EINVAL: what ..._preview refuses of a preview, a NULL preview, rows_dev NULL, n_ticks < 0. */
+int cgmres_hip_preview_device(cgmres_hip_handle h, const cgmres_hip_loop_preview* preview, int32_t n_ticks, void* rows_dev);
 int cgmres_hip_synchronize(cgmres_hip_handle h);
 
 /* ---- state: the private members of Cgmres (cgmres.hpp:195-202) and Gmres (gmres.hpp:120-124) ------ */
